@@ -1,6 +1,10 @@
 """ELBO-step throughput of the MI355X CBF-SSM hot path (BASELINE.json metric) -- prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--mode eval|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--mode eval|train] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the line.
+Everything else the line can carry is measured only with --full: the per-kernel roofline, the CPU baseline and, at N>1,
+the single-rank baseline, the C4 config and the collective (below).
 
 A "step" is one pass of the hot path over one synthetic mini-batch already resident in HBM: noise draw, positivity
 transforms, K_mm/Cholesky/K^-1 + operand packing for both GPs, both backward (recognition) runs, the forward
@@ -33,6 +37,20 @@ F64_MFMA_PEAK_TFLOPS = 78.6   # MI355X FP64 matrix (spec); csrc/probe/mfma_f64_p
 F32_MFMA_PEAK_TFLOPS = 157.3  # MI355X FP32 matrix, v_mfma_f32_16x16x4_f32 at 32 cycles per SIMD (MI355X_MICROARCH.md: 155 measured;
                               # csrc/probe/mfma_f64_probe prints the rate it measures on the box)
 HBM_PEAK_GBS = 8000.0
+DUMP_BYTES = 60 * 10 ** 6     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: what the timed path computed in its last step, one float64 `<outdir>/<name>.npy` per array.  An array
+    larger than its share of DUMP_BYTES is written as an evenly strided sample of its elements (flattened; the same elements
+    in every run)."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays)) // 8
+    for name, t in arrays.items():
+        a = t.detach().to('cpu', torch.float64).numpy()
+        if a.size > share:
+            a = a.reshape(-1)[::-(-a.size // share)]
+        np.save(os.path.join(outdir, name + '.npy'), a)
 
 
 def _cpu_model():
@@ -182,11 +200,15 @@ def bench_variant(args, dev):
     noise_pipe = ops.NoisePipeline(dev, g, with_backward=False)
     stepper = HipHalfTrainStep(eng, opt)                  # one HIP-graph replay per train step (CBFSSM_HIP_GRAPH=0: eager)
 
+    last_terms = {}
+
     def step():
         noise = noise_pipe.next(w.T, w.N)
         if mode == 'train':
             return stepper.step(u, y, noise, True)
-        return eng.forward(params, u, y, noise, True)[0]
+        loss_t, terms, _ = eng.forward(params, u, y, noise, True)
+        last_terms.update(terms)
+        return loss_t
 
     for _ in range(args.warmup):
         out = step()
@@ -198,35 +220,51 @@ def bench_variant(args, dev):
     dt = time.perf_counter() - t0
     loss = float(out)
     assert np.isfinite(loss), 'non-finite loss'
+    if args.dump_outputs:
+        arrays = {'loss': out}
+        if mode == 'train':
+            arrays.update(('elbo_' + k, v) for k, v in stepper.last_terms.items())
+            arrays.update(('param_' + k.replace('.', '_'), v) for k, v in stepper.opt.views.items())
+        else:
+            arrays.update(('elbo_' + k, v) for k, v in last_terms.items())
+            arrays.update(pred_mean=eng.last_ws.pred_mean, pred_var=eng.last_ws.pred_var)
+        dump_outputs(args.dump_outputs, arrays)
 
-    # ---- the time-loop kernels by themselves: every launch of a step bracketed by HIP events (eng._prof)
-    ms, n = {}, {}
-    stepper.use_graph = False                             # (eager launches, each bracketed by events)
-    for _ in range(3):
-        eng._prof = []
-        step()
-        torch.cuda.synchronize()
+    roof = None
+    if args.full:
+        # ---- the time-loop kernels by themselves: every launch of a step bracketed by HIP events (eng._prof)
         ms, n = {}, {}
-        for kind, e0, e1 in eng._prof:
-            ms[kind] = ms.get(kind, 0.0) + e0.elapsed_time(e1)
-            n[kind] = n.get(kind, 0) + 1
-    eng._prof = None
+        stepper.use_graph = False                             # (eager launches, each bracketed by events)
+        for _ in range(3):
+            eng._prof = []
+            step()
+            torch.cuda.synchronize()
+            ms, n = {}, {}
+            for kind, e0, e1 in eng._prof:
+                ms[kind] = ms.get(kind, 0.0) + e0.elapsed_time(e1)
+                n[kind] = n.get(kind, 0) + 1
+        eng._prof = None
 
-    def F(M, D, Do):   # algorithmic FLOPs of one GP point evaluation
-        return 2 * M * M + M * (2 * D + 5 * Do + 5)
-    pts = 1.0 * (w.T - 1) * w.N
-    fl = {'forward_pass': pts * F(w.M, w.D, w.dim_x)}
-    if mode == 'train':
-        stash = eng.stash and not f32                                  # (the float32 adjoint is one launch at every height)
-        fa = 2.0 if eng.last_ws.a2s_f is not None else 3.0            # saved A2 tiles: the reverse sweep costs 2 F
-        outer = 2.0 * w.M * w.M if stash else 0.0                      # stash mode: A2bar K^T runs in the contraction
-        fl['forward_pass_adjoint'] = pts * (fa * F(w.M, w.D, w.dim_x) - outer)
-        if stash:
-            fl['stash_contraction'] = pts * outer
-    name = max(ms, key=lambda k: ms[k])
-    ach = fl[name] / (ms[name] * 1e-3) / 1e12
+        def F(M, D, Do):   # algorithmic FLOPs of one GP point evaluation
+            return 2 * M * M + M * (2 * D + 5 * Do + 5)
+        pts = 1.0 * (w.T - 1) * w.N
+        fl = {'forward_pass': pts * F(w.M, w.D, w.dim_x)}
+        if mode == 'train':
+            stash = eng.stash and not f32                                  # (the float32 adjoint is one launch at every height)
+            fa = 2.0 if eng.last_ws.a2s_f is not None else 3.0            # saved A2 tiles: the reverse sweep costs 2 F
+            outer = 2.0 * w.M * w.M if stash else 0.0                      # stash mode: A2bar K^T runs in the contraction
+            fl['forward_pass_adjoint'] = pts * (fa * F(w.M, w.D, w.dim_x) - outer)
+            if stash:
+                fl['stash_contraction'] = pts * outer
+        name = max(ms, key=lambda k: ms[k])
+        ach = fl[name] / (ms[name] * 1e-3) / 1e12
+        peak = F32_MFMA_PEAK_TFLOPS if f32 else F64_MFMA_PEAK_TFLOPS
+        roof = {'bound': 'mfma', 'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s',
+                'frac': ach / peak, 'traffic': None, 'kernel': name,
+                'kernel_ms': ms, 'kernel_tflops': {k: fl[k] / (ms[k] * 1e-3) / 1e12 for k in ms}, 'launches': n,
+                'note': 'one GP (gp_f), no backward runs: one workgroup per 16-chain group walks the T - 1 steps (%d groups on '
+                        'the chip\'s CUs); full launches, HIP events on the launch stream' % ((w.N + 15) // 16)}
     steps_per_s = args.steps / dt
-    peak = F32_MFMA_PEAK_TFLOPS if f32 else F64_MFMA_PEAK_TFLOPS
     rec = {
         'metric': 'ELBO steps/sec', 'value': steps_per_s, 'unit': 'steps/s (one step = one %d-sequence mini-batch per GPU)' % w.B,
         'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
@@ -237,11 +275,7 @@ def bench_variant(args, dev):
                                                       w.B, w.S, w.dim_x, w.dim_u, w.dim_y, w.recog_len),
                    'model': args.model, 'mode': mode, 'global_batch': w.B, 'seq_len': w.T, 'particles': w.S, 'parallelism': 'dp1'},
         'loss': loss,
-        'roofline': {'bound': 'mfma', 'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s',
-                     'frac': ach / peak, 'traffic': None, 'kernel': name,
-                     'kernel_ms': ms, 'kernel_tflops': {k: fl[k] / (ms[k] * 1e-3) / 1e12 for k in ms}, 'launches': n,
-                     'note': 'one GP (gp_f), no backward runs: one workgroup per 16-chain group walks the T - 1 steps (%d groups on '
-                             'the chip\'s CUs); full launches, HIP events on the launch stream' % ((w.N + 15) // 16)},
+        'roofline': roof,
         'cpu_baseline': None,
     }
     print(json.dumps(rec))
@@ -268,6 +302,11 @@ def main():
     ap.add_argument('--dtype', default='float64', choices=['float64', 'float32'],
                     help='float32: the float32-arithmetic passes and adjoint (NOT the headline: the reference computes in '
                          'float64)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float64)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the per-kernel roofline, the CPU baseline '
+                         '(unless --no-cpu-baseline) and, at N > 1, the single-rank baseline, the C4 config and the collective')
     args = ap.parse_args()
 
     from cbfssm import synthetic as syn
@@ -346,6 +385,14 @@ def main():
             b['stepper'] = stepper
             b['step'] = lambda: stepper.step(u, y, draw_noise(), condition=True)
             b['step_local'] = lambda: stepper.step(u, y, draw_noise(), condition=True, local=True)
+
+            def outputs(loss):
+                # the step's loss and ELBO terms, and the parameters after its Adam update
+                d = {'loss': loss}
+                d.update(('elbo_' + k, v) for k, v in stepper.last_terms.items())
+                d.update(('param_' + k.replace('.', '_'), v) for k, v in stepper.params.items())
+                return d
+            b['outputs'] = outputs
         else:
             from cbfssm.hip.train import HipElboGrad
             eng = HipElboGrad(cfg, dev, dist if world > 1 else None, require_adjoint=False, dtype=args.dtype)
@@ -359,10 +406,13 @@ def main():
                 return out8
             b['step'] = step
             b['step_local'] = lambda: step(local=True)
+            # out[0..7] of cbfssm_elbo_combine_f64 (loss = out[6]) and the predictive moments of the same evaluation
+            b['outputs'] = lambda out: {'elbo_out': out, 'pred_mean': eng.last_ws.pred_mean, 'pred_var': eng.last_ws.pred_var}
         return b
 
     def timed(stepfn, steps, warmup):
-        """`warmup` untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides; max over ranks"""
+        """`warmup` untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides; max over ranks.
+        Returns (seconds, loss, what the last step returned)."""
         out = None
         for _ in range(warmup):
             out = stepfn()
@@ -378,21 +428,23 @@ def main():
             dt = float(tmax.item())
         loss = float(out[6]) if mode == 'eval' else float(out)
         assert np.isfinite(loss), 'non-finite loss'
-        return dt, loss
+        return dt, loss, out
 
     def with_baseline(b, steps, warmup):
         """N > 1: the single-rank baseline of the SAME workload in the SAME run -- the same launches on every rank with the
         collective off (each rank evaluates its own mini-batch as a single device would; max over ranks like `value`)"""
-        dt1, _ = timed(b['step_local'], steps, max(1, min(warmup, 2)))
+        dt1, _, _ = timed(b['step_local'], steps, max(1, min(warmup, 2)))
         return {'ms_per_step': dt1 / steps * 1e3, 'steps_per_s': steps / dt1, 'steps': steps,
                 'how': 'the same step on every rank with the all-reduce off, same process, right after the timed region'}
 
     bld = build(w, cfg)
     u, y, params, draw_noise, stepper = bld['u'], bld['y'], bld['params'], bld['draw_noise'], bld['stepper']
     N = w.N
-    dt, loss = timed(bld['step'], args.steps, args.warmup)
+    dt, loss, out = timed(bld['step'], args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bld['outputs'](out))
     single = eff = c4 = None
-    if world > 1:
+    if world > 1 and args.full:
         single = with_baseline(bld, args.steps, args.warmup)
         eff = (args.steps / dt) / single['steps_per_s']
         if default_workload and mode == 'train' and not os.environ.get('CBFSSM_BENCH_NO_C4'):
@@ -401,7 +453,7 @@ def main():
             w4 = syn.WORKLOADS['C4']
             k4 = max(3, min(args.steps, 10))
             b4 = build(w4, w4.model_config())
-            dt4, loss4 = timed(b4['step'], k4, 2)
+            dt4, loss4, _ = timed(b4['step'], k4, 2)
             s4 = with_baseline(b4, k4, 2)
             c4 = {'workload': '%s %s step: M=%d T=%d B=%d/GPU S=%d' % (w4.name, mode, w4.M, w4.T, w4.B, w4.S),
                   'value': k4 / dt4 * world, 'unit': 'steps/s', 'steps': k4, 'ms_per_step': dt4 / k4 * 1e3,
@@ -414,7 +466,7 @@ def main():
     # ---- the step's ONE collective, timed by itself on every rank (all ranks take part; rank 0 reports): HIP events on
     # the launch stream for RCCL, wall clock around a synchronised call for the gloo rehearsal
     coll = None
-    if world > 1:
+    if world > 1 and args.full:
         from cbfssm.hip.dist_utils import all_reduce_sum
         nel = int(stepper.engine.red.numel()) if mode == 'train' else 3
         buf = torch.ones(nel, dtype=torch.float64, device=dev)
@@ -447,7 +499,7 @@ def main():
 
     # ---- per-kernel timing of the time-loop kernels with HIP events on the launch stream
     roof = None
-    if rank == 0 and args.dtype == 'float32':
+    if rank == 0 and args.full and args.dtype == 'float32':
         # the float32-arithmetic time loops (cbfssm_*_pass_f32, cbfssm_*_pass_bwd_f32), each timed by itself with HIP events on
         # the launch stream and priced against the float32 matrix peak (v_mfma_f32_16x16x4_f32)
         import ctypes as C
@@ -511,7 +563,7 @@ def main():
                 'kernel_tflops': {k: v[1] / v[0] / 1e12 for k, v in kern.items()},
                 'note': 'float32 arithmetic (v_mfma_f32_16x16x4_f32, 32 cycles per SIMD: 157.3 TFLOP/s); full launches; the adjoint is '
                         'priced at 2 F per GP evaluation when it reads the kept [A2 | kernel tile] records, 3 F when it recomputes them'}
-    elif rank == 0:
+    elif rank == 0 and args.full:
         import ctypes as C
         l = lib.load()
         st = ops._stream()
@@ -710,7 +762,7 @@ def main():
             'params': args.params,
             'roofline': roof,
         }
-        if not args.no_cpu_baseline and world == 1 and args.dtype == 'float64':
+        if args.full and not args.no_cpu_baseline and world == 1 and args.dtype == 'float64':
             rec['cpu_baseline'] = cpu_baseline(w, mode, policy=args.cpu_baseline)
             rec['speedup_vs_cpu_baseline'] = rec['value'] / rec['cpu_baseline']['value']
         else:

@@ -1,10 +1,12 @@
 """The driver's bench contract: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with the agreed
-keys, including the `roofline` and `cpu_baseline` objects (run on the smallest workload so that it takes seconds)."""
+keys; with `--full` the line also holds the `roofline` and `cpu_baseline` objects (run on the smallest workload so that it
+takes seconds)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +24,7 @@ def _run(*args):
 
 @pytest.mark.parametrize('mode', ['train', 'eval'])
 def test_bench_line_has_the_contract_keys(mode):
-    rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--mode', mode)
+    rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--mode', mode, '--full')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in rec, k
@@ -41,11 +43,35 @@ def test_bench_line_has_the_contract_keys(mode):
     assert cpu['kind'] == 'port' and cpu['value'] > 0 and cpu['cores'] >= 1
 
 
+@pytest.mark.parametrize('mode', ['train', 'eval'])
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(mode, tmp_path):
+    """Without `--full` the line measures the headline only; `--dump-outputs DIR` writes what the last timed step computed,
+    float64, and two runs with the same arguments write the same arrays (the inputs are seeded)."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / str(run)
+        rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--mode', mode, '--dump-outputs', str(d))
+        assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['value'] == pytest.approx(1e3 / rec['ms_per_step'], rel=1e-6)
+        assert rec['roofline'] is None and rec['cpu_baseline'] is None
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    a, b = dumps
+    assert set(a) == set(b)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.all(np.isfinite(a[k])), k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-9, atol=0, err_msg=k)
+    if mode == 'train':
+        assert float(b['loss']) == pytest.approx(rec['loss'], rel=1e-12)
+        assert sum(k.startswith('param_') for k in b) == 12 and 'elbo_loglik' in b
+    else:
+        assert float(b['elbo_out'][6]) == pytest.approx(rec['loss'], rel=1e-12)
+        assert b['pred_mean'].shape == b['pred_var'].shape == (16, 50, 1)
+
+
 def test_float32_bench_line_has_a_roof():
     """`--dtype float32` (the reference's model dtype argument): the float32 kernels timed like the float64 ones, against the
     float32 matrix peak."""
     rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--mode', 'train', '--dtype', 'float32',
-               '--no-cpu-baseline')
+               '--no-cpu-baseline', '--full')
     roof = rec['roofline']
     assert rec['dtype'] == 'f32' and roof['bound'] == 'mfma' and roof['peak'] == pytest.approx(157.3)
     assert roof['frac'] == pytest.approx(roof['achieved'] / roof['peak']) and roof['achieved'] > 0
@@ -56,13 +82,14 @@ def test_float32_bench_line_has_a_roof():
 @pytest.mark.parametrize('model', ['half', 'prssm'])
 def test_variant_bench_lines(model):
     """`--model half|prssm`: the forward-only variants have a bench line with a roof."""
-    rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--model', model)
+    rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--model', model, '--full')
     assert rec['config']['model'] == model and rec['config']['mode'] == 'train' and rec['value'] > 0
     roof = rec['roofline']
     assert roof['bound'] == 'mfma' and roof['frac'] == pytest.approx(roof['achieved'] / roof['peak'])
     assert set(roof['kernel_ms']) == {'forward_pass', 'forward_pass_adjoint'}
     # ... and in float32 arithmetic against the float32 matrix peak
-    rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--model', model, '--dtype', 'float32')
+    rec = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C1', '--model', model, '--dtype', 'float32',
+               '--full')
     assert rec['dtype'] == 'f32' and rec['roofline']['peak'] == pytest.approx(157.3) and rec['value'] > 0
     assert set(rec['roofline']['kernel_ms']) == {'forward_pass', 'forward_pass_adjoint'}
 
@@ -74,7 +101,7 @@ def test_two_rank_bench_line_on_one_device():
     env = dict(os.environ, CBFSSM_BENCH_ONE_DEVICE='1')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                           '127.0.0.1', '--master-port', '29541', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3',
-                          '--warmup', '1'], capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)
+                          '--warmup', '1', '--full'], capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, out.stdout[-2000:]
