@@ -339,55 +339,129 @@ class ElboWorkspace:
         self.out = torch.zeros(8, **f)
 
 
-def elbo_forward(prob, pack_f, pack_b, var_x, var_y, u, y, hid_b, eps_b, eps_f, loss_factors, ws=None,
-                 keep_h=False, f32=False, bf16=False):
-    """One forward evaluation of the ELBO (cbfssm.py:84-271) from prepared GP packs.  Asynchronous.
-
-    Returns the workspace; ws.out = [loglik, kl_x, entropy, kl_z_f, kl_z_b, elbo, loss, info].
-    """
+def reduce_partials(gpart, slab, n, out, st):
+    """out = the sum of the first n per-workgroup slabs of `slab` doubles in gpart (cbfssm_reduce_partials_f64)."""
     lib = _l.load()
-    dev = u.device
-    if ws is None:
-        ws = ElboWorkspace(prob, dev, keep_h)
-    st = _stream()
-    pb = C.byref(prob)
+    _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), slab, n, _ptr(out), st), 'cbfssm_reduce_partials_f64')
+
+
+class TimeLoops:
+    """The time-loop entry points (include/cbfssm_hip.h) bound to the operands of one evaluation: the problem, its
+    workspace, the GP packs (pack_b None: forward-only variants), constrained var_x / var_y, inputs, noise and the loss
+    factors cL / cE of the adjoints.  Every pass takes the problem it runs -- `prob` or a chain-group piece of it
+    (HipElboGrad._sub_problem) -- and the stream.  f32: the float32-arithmetic symbols, which read the packs' float32
+    images (`cast_f32`; the float64 pack and the storage stay float64)."""
+
+    def __init__(self, prob, ws, pack_f, pack_b, var_x, var_y, u, y, eps_f, hid_b=None, eps_b=None, x0=None,
+                 cL=0.0, cE=0.0, f32=False, bf16=False):
+        self.prob, self.ws, self.pack_f, self.pack_b = prob, ws, pack_f, pack_b
+        self.var_x, self.var_y, self.u, self.y, self.x0, self.eps_f, self.hid_b, self.eps_b = \
+            var_x, var_y, u, y, x0, eps_f, hid_b, eps_b
+        self.cL, self.cE, self.f32, self.bf16 = cL, cE, f32, bf16
+
+    def cast_f32(self):
+        """float32: the packs' float32 images of this evaluation's prepare (one launch per pack, backward GP first)"""
+        for pk in (self.pack_b, self.pack_f):
+            if self.f32 and pk is not None:
+                pk.pack_f32(self.bf16)
+
+    def _gp(self, pack):
+        return C.c_void_p(pack.buf32.data_ptr()) if self.f32 else _ptr(pack.buf)
+
+    def _check(self, rc, name):
+        _l.check(rc, 'cbfssm_%s_%s' % (name, 'f32' if self.f32 else 'f64'))
+
+    def _fwd_args(self, q, *mid):
+        """the leading arguments of the forward-direction passes; mid: y2 (CBFSSM) or x0 (half_forward_pass)"""
+        ws = self.ws
+        return ((C.byref(q), C.byref(self.pack_f.layout), self._gp(self.pack_f), _ptr(self.var_x), _ptr(self.var_y),
+                 _ptr(self.u), _ptr(self.y)) + tuple(_ptr(t) for t in mid) +
+                (_ptr(self.eps_f) if self.eps_f.numel() else None, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f)))
+
+    def _bwd_args(self, q):
+        return (C.byref(q), C.byref(self.pack_b.layout), self._gp(self.pack_b), _ptr(self.var_x), _ptr(self.u),
+                _ptr(self.y), _ptr(self.hid_b), _ptr(self.eps_b))
+
+    def backward_pass(self, q, st):
+        lib, ws = _l.load(), self.ws
+        a = self._bwd_args(q) + (_ptr(ws.y2), _ptr(ws.h_all), _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.ent_part), st)
+        self._check(lib.cbfssm_backward_pass_f32(*a) if self.f32 else lib.cbfssm_backward_pass_f64(*a), 'backward_pass')
+
+    def forward_pass(self, q, st):
+        lib = _l.load()
+        a = self._fwd_args(q, self.ws.y2) + (_ptr(self.ws.kl_part), st)
+        self._check(lib.cbfssm_forward_pass_f32(*a) if self.f32 else lib.cbfssm_forward_pass_f64(*a), 'forward_pass')
+
+    def forward_pass_bwd(self, q, st, chunk=None):
+        """chunk = (t_hi, t_lo, stash_a, stash_k, cols): one stash-mode launch over steps t_hi .. t_lo (float64, M > 112)"""
+        lib, ws = _l.load(), self.ws
+        a = self._fwd_args(q, ws.y2) + (self.cL, _ptr(ws.gy2), _ptr(ws.gpart_f))
+        if chunk is None:
+            self._check(lib.cbfssm_forward_pass_bwd_f32(*a, st) if self.f32 else lib.cbfssm_forward_pass_bwd_f64(*a, st),
+                        'forward_pass_bwd')
+        else:
+            t_hi, t_lo, sa, sk, cols = chunk
+            _l.check(lib.cbfssm_forward_pass_bwd_ex_f64(*a, t_hi, t_lo, _ptr(ws.gx_carry), _ptr(sa), _ptr(sk), cols, st),
+                     'cbfssm_forward_pass_bwd_ex_f64')
+
+    def backward_pass_bwd(self, q, st, chunk=None):
+        """chunk = (seg0, seg1, stash_a, stash_k, cols): one stash-mode launch over the segments [seg0, seg1) of both runs"""
+        lib, ws = _l.load(), self.ws
+        a = self._bwd_args(q) + (_ptr(ws.h_all), _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.gy2), self.cE, _ptr(ws.gpart_b))
+        if chunk is None:
+            self._check(lib.cbfssm_backward_pass_bwd_f32(*a, st) if self.f32 else lib.cbfssm_backward_pass_bwd_f64(*a, st),
+                        'backward_pass_bwd')
+        else:
+            seg0, seg1, sa, sk, cols = chunk
+            _l.check(lib.cbfssm_backward_pass_bwd_ex_f64(*a, seg0, seg1, 1, _ptr(sa), _ptr(sk), cols, st),
+                     'cbfssm_backward_pass_bwd_ex_f64')
+
+    def half_forward_pass(self, q, st):
+        lib = _l.load()
+        a = self._fwd_args(q, self.x0) + (_ptr(self.ws.kl_part), st)
+        self._check(lib.cbfssm_half_forward_pass_f32(*a) if self.f32 else lib.cbfssm_half_forward_pass_f64(*a),
+                    'half_forward_pass')
+
+    def half_forward_pass_bwd(self, q, st, chunk=None):
+        """chunk = (t_hi, t_lo, stash_a, stash_k, cols): one stash-mode launch (float64, M > 112); None: the whole sweep"""
+        lib, ws = _l.load(), self.ws
+        a = self._fwd_args(q) + (self.cL, _ptr(ws.gx0), _ptr(ws.gpart_f))
+        if self.f32:
+            rc = lib.cbfssm_half_forward_pass_bwd_f32(*a, st)
+        else:
+            t_hi, t_lo, sa, sk, cols = chunk or (q.T - 2, 0, None, None, 0)
+            rc = lib.cbfssm_half_forward_pass_bwd_f64(*a, t_hi, t_lo, _ptr(ws.gx_carry) if chunk else None, _ptr(sa),
+                                                      _ptr(sk), cols, st)
+        self._check(rc, 'half_forward_pass_bwd')
+
+    def elbo_tail(self, lf0, lf1, st, kl_pack=None):
+        """log-likelihood + predictive moments, then ws.out = [loglik, kl_x, entropy, kl_z_f, kl_z_b, elbo, loss, info];
+        kl_pack: the pack whose prior KL counts (default pack_f)"""
+        lib, ws, pb = _l.load(), self.ws, C.byref(self.prob)
+        _l.check(lib.cbfssm_loglik_moments_f64(pb, _ptr(self.var_y), _ptr(self.y), _ptr(ws.x), _ptr(ws.ll_part),
+                                               _ptr(ws.pred_mean), _ptr(ws.pred_var), _ptr(ws.int_mean),
+                                               _ptr(ws.int_var), st), 'cbfssm_loglik_moments_f64')
+        b = self.pack_b is not None             # (forward-only variants: no entropy term, no backward GP)
+        _l.check(lib.cbfssm_elbo_combine_f64(pb, float(lf0), float(lf1), _ptr(ws.ll_part), ws.ll_part.numel(),
+                                             _ptr(ws.kl_part), ws.kl_part.numel(), _ptr(ws.ent_part) if b else None,
+                                             ws.ent_part.numel() if b else 0, _ptr((kl_pack or self.pack_f).scal),
+                                             _ptr(self.pack_b.scal) if b else None, _ptr(ws.out), st),
+                 'cbfssm_elbo_combine_f64')
+
+
+def elbo_forward(lp, loss_factors):
+    """One forward evaluation of the ELBO (cbfssm.py:84-271) from prepared GP packs, bound in the TimeLoops `lp`.
+    Asynchronous.  Returns the workspace; ws.out = [loglik, kl_x, entropy, kl_z_f, kl_z_b, elbo, loss, info]."""
+    prob, st = lp.prob, _stream()
     N = prob.B * prob.S
-    assert u.shape == (prob.B, prob.T, prob.dim_u) and y.shape == (prob.B, prob.T, prob.dim_y)
-    assert hid_b.numel() == 2 * prob.T * N and eps_b.numel() == 2 * prob.T * N
-    assert eps_f.numel() == (prob.T - 1) * N
-    if f32:
-        # float32 arithmetic in the time loops (cbfssm_*_pass_f32), float64 storage; forward evaluation only
-        b32, f32p = pack_b.pack_f32(bf16), pack_f.pack_f32(bf16)
-        rc = lib.cbfssm_backward_pass_f32(pb, C.byref(pack_b.layout), C.c_void_p(b32.data_ptr()), _ptr(var_x), _ptr(u),
-                                          _ptr(y), _ptr(hid_b), _ptr(eps_b), _ptr(ws.y2), _ptr(ws.h_all), _ptr(ws.fmv_b),
-                                          _ptr(ws.a2s_b), _ptr(ws.ent_part), st)
-        _l.check(rc, 'cbfssm_backward_pass_f32')
-        rc = lib.cbfssm_forward_pass_f32(pb, C.byref(pack_f.layout), C.c_void_p(f32p.data_ptr()), _ptr(var_x), _ptr(var_y),
-                                         _ptr(u), _ptr(y), _ptr(ws.y2), _ptr(eps_f) if eps_f.numel() else None,
-                                         _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), _ptr(ws.kl_part), st)
-        _l.check(rc, 'cbfssm_forward_pass_f32')
-        return _elbo_tail(lib, pb, prob, pack_f, pack_b, var_y, y, loss_factors, ws, st)
-    rc = lib.cbfssm_backward_pass_f64(pb, C.byref(pack_b.layout), _ptr(pack_b.buf), _ptr(var_x), _ptr(u), _ptr(y),
-                                      _ptr(hid_b), _ptr(eps_b), _ptr(ws.y2), _ptr(ws.h_all), _ptr(ws.fmv_b),
-                                      _ptr(ws.a2s_b), _ptr(ws.ent_part), st)
-    _l.check(rc, 'cbfssm_backward_pass_f64')
-    rc = lib.cbfssm_forward_pass_f64(pb, C.byref(pack_f.layout), _ptr(pack_f.buf), _ptr(var_x), _ptr(var_y),
-                                     _ptr(u), _ptr(y), _ptr(ws.y2), _ptr(eps_f) if eps_f.numel() else None,
-                                     _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), _ptr(ws.kl_part), st)
-    _l.check(rc, 'cbfssm_forward_pass_f64')
-    return _elbo_tail(lib, pb, prob, pack_f, pack_b, var_y, y, loss_factors, ws, st)
-
-
-def _elbo_tail(lib, pb, prob, pack_f, pack_b, var_y, y, loss_factors, ws, st):
-    rc = lib.cbfssm_loglik_moments_f64(pb, _ptr(var_y), _ptr(y), _ptr(ws.x), _ptr(ws.ll_part), _ptr(ws.pred_mean),
-                                       _ptr(ws.pred_var), _ptr(ws.int_mean), _ptr(ws.int_var), st)
-    _l.check(rc, 'cbfssm_loglik_moments_f64')
-    rc = lib.cbfssm_elbo_combine_f64(pb, float(loss_factors[0]), float(loss_factors[1]),
-                                     _ptr(ws.ll_part), ws.ll_part.numel(), _ptr(ws.kl_part), ws.kl_part.numel(),
-                                     _ptr(ws.ent_part), ws.ent_part.numel(), _ptr(pack_f.scal), _ptr(pack_b.scal),
-                                     _ptr(ws.out), st)
-    _l.check(rc, 'cbfssm_elbo_combine_f64')
-    return ws
+    assert lp.u.shape == (prob.B, prob.T, prob.dim_u) and lp.y.shape == (prob.B, prob.T, prob.dim_y)
+    assert lp.hid_b.numel() == 2 * prob.T * N and lp.eps_b.numel() == 2 * prob.T * N
+    assert lp.eps_f.numel() == (prob.T - 1) * N
+    lp.cast_f32()
+    lp.backward_pass(prob, st)
+    lp.forward_pass(prob, st)
+    lp.elbo_tail(loss_factors[0], loss_factors[1], st)
+    return lp.ws
 
 
 def tf_forward(x):
@@ -443,9 +517,8 @@ class HipElbo:
             self._ws[key] = ElboWorkspace(prob, self.device, keep_h)
         ws = self._ws[key]
         hid_b, eps_b, eps_f = (_f64(noise[k], self.device) for k in ('hid_b', 'eps_b', 'eps_f'))
-        elbo_forward(prob, self.pack_f, self.pack_b, self.var_x, self.var_y, u, y, hid_b, eps_b, eps_f,
-                     self.config['loss_factors'], ws, f32=self.f32, bf16=self.bf16)
-        return ws
+        return elbo_forward(TimeLoops(prob, ws, self.pack_f, self.pack_b, self.var_x, self.var_y, u, y, eps_f, hid_b, eps_b,
+                                      f32=self.f32, bf16=self.bf16), self.config['loss_factors'])
 
 
 class NoisePipeline:

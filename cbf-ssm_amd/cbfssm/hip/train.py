@@ -69,7 +69,7 @@ class StashContract:
     def add(self, sa, sk, cols, stream):
         lib = _l.load()
         nslots = cols // 16
-        if nslots <= 0 or os.environ.get('CBFSSM_DIAG_SKIP_CONTRACT'):     # (diagnostic: what the contraction costs a step)
+        if nslots <= 0:
             return
         need = int(lib.cbfssm_stash_contract_work_elems(C.byref(self.pack.layout), nslots))
         if self.work is None or self.work.numel() < need:
@@ -80,6 +80,55 @@ class StashContract:
     def dense(self):
         nb = self.pack.layout.NBLK
         return _unpack_c(self.image, nb, nb)
+
+
+def _timed(prof, kind, stream, fn):
+    """Measurement hook (bench.py): with a list in an engine's `_prof`, the launches of fn() are bracketed by HIP events
+    on `stream` (None: the current one), so that each kernel's own time can be summed per kind."""
+    if prof is None:
+        return fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    fn()
+    e1.record(stream)
+    prof.append((kind, e0, e1))
+
+
+# ---- float32 adjoint.  It writes the non-stash slab at every tile height: its matrix section holds
+# G = K^-1 (d loss / d K^-1) K^-1, the data part of d loss / d K_mm itself (full up to 10 row blocks, the lower-triangular
+# blocks of G + G^T from 13: include/cbfssm_hip.h).  The float64 slab of the stash tile heights (M > 112) has no matrix
+# section: there the reduced float32 slab is re-packed into that layout plus the image the train tail takes in stash mode.
+def repacks_f32(f32, layout):
+    """float32 at a stash tile height: the reduced float32 slab goes through repack_f32"""
+    return bool(f32 and layout.rev_stash)
+
+
+def repack_f32(t32, slab, img, nb):
+    """reduced float32 slab t32 = [mubar | s2bar | G | rest] -> slab = [mubar | s2bar | rest], img = G"""
+    og, nimg = 2 * nb * 256, nb * nb * 256
+    slab[:og].copy_(t32[:og])
+    slab[og:].copy_(t32[og + nimg:])
+    img.copy_(t32[og:og + nimg])
+
+
+def g_mode(f32, layout):
+    """the train tail's reading of the matrix section: 0 d loss / d K^-1 (float64 adjoint), 1 G, 2 G's lower block triangle"""
+    return 0 if not f32 else (2 if layout.NBLK >= 13 else 1)
+
+
+def kgk_image(pack, slab, img=None):
+    """CBFSSM_TORCH_TAIL after a float32 adjoint: _gp_adjoint expects d loss / d K^-1 = K G K, K = K_mm + jitter I, as a
+    C-layout image.  G: the matrix section of `slab`, or the re-packed `img` at the stash tile heights."""
+    nb, M, dev = pack.layout.NBLK, pack.M, pack.buf.device
+    G = _unpack_c(img if img is not None else slab[2 * nb * 256:2 * nb * 256 + nb * nb * 256], nb, nb)
+    if g_mode(True, pack.layout) == 2:          # lower-triangular blocks of G + G^T (diagonal blocks: of G)
+        blk = torch.arange(16 * nb, device=dev) // 16
+        G = torch.where(blk[:, None] >= blk[None, :], G, torch.zeros_like(G))
+    G = 0.5 * (G + G.T)[:M, :M]
+    K = pack.Kmm + pack.scal[_l.SCAL_JITTER] * torch.eye(M, dtype=torch.float64, device=dev)
+    Bd = torch.zeros(16 * nb, 16 * nb, dtype=torch.float64, device=dev)
+    Bd[:M, :M] = K @ G @ K
+    return Bd.view(nb, 4, 4, nb, 16).permute(0, 3, 1, 2, 4).reshape(-1)
 
 
 class HipElboGrad:
@@ -116,6 +165,8 @@ class HipElboGrad:
             # per-workgroup slabs of the float32 adjoint: the non-stash layout at every tile height (Kinvbar included)
             self.slab32_f = int(_l.load().cbfssm_rev32_slab_elems(C.byref(self.pack_f.layout)))
             self.slab32_b = int(_l.load().cbfssm_rev32_slab_elems(C.byref(self.pack_b.layout)))
+        self.repack32 = repacks_f32(self.f32, self.pack_f.layout)
+        self._tmp32 = None
         self.last_ws = None
         # flat reduce buffer: [slab_f | slab_b | loglik, kl_x, entropy, gvy_ll[dim_y] | stash mode: the two contracted
         # d loss / d K^-1 images] -- everything a data-parallel step exchanges, in ONE all-reduce
@@ -178,21 +229,13 @@ class HipElboGrad:
         """Loss only (what Trainer's test pass and Outputs fetch): returns (loss 0-d tensor, terms, workspace).
         Data parallel: `weight` scales this rank's data terms in the all-reduce (0 for a stand-in shard on a rank that
         got no sequence); `local=True` evaluates without the collective (every rank holds the whole batch)."""
-        dev = self.device
-        cfg = self.config
-        u, y = _f64(u, dev), _f64(y, dev)
-        B, T = u.shape[0], u.shape[1]
-        prob = _l.make_problem(B, self.S, T, self.dim_x, self.dim_u, self.dim_y, self.M, cfg['recog_len'],
-                               cfg['k_factor'], condition)
-        p, c = self._constrained_flat(self._flat(params))
-        ops.prepare_pair(self.pack_f, (p['f.zeta_pos'], c['f.ls'], c['f.var'], p['f.zeta_mean'], c['f.zvar']),
-                         self.pack_b, (p['b.zeta_pos'], c['b.ls'], c['b.var'], p['b.zeta_mean'], c['b.zvar']))
-        key = ('eval', B, T)
+        u, y, prob, _, p, c = self._prepare(params, u, y, condition)
+        key = ('eval', prob.B, prob.T)
         if key not in self._ws:
-            self._ws[key] = ops.ElboWorkspace(prob, dev, keep_h=False)
+            self._ws[key] = ops.ElboWorkspace(prob, self.device, keep_h=False)
         ws = self._ws[key]
-        hid_b, eps_b, eps_f = (_f64(noise[k], dev) for k in ('hid_b', 'eps_b', 'eps_f'))
-        self._elbo_forward(prob, ws, c, u, y, hid_b, eps_b, eps_f)
+        lp = self._loops(prob, ws, c, u, y, noise)
+        self._elbo_forward(lp)
         out = ws.out
         if self.dist is not None and not local:
             # data terms summed over the ranks' shards, prior KL counted once (cbfssm.py:257-261)
@@ -200,9 +243,7 @@ class HipElboGrad:
             if weight != 1.0:
                 red.mul_(float(weight))
             all_reduce_sum(red, self.dist)
-            lf = cfg['loss_factors']
-            cL, cE = float(lf[0]) / self.S, float(lf[1]) / self.S
-            loss = -(red[0] * cL - red[1] * cL + red[2] * cE - out[3] - out[4])
+            loss = -(red[0] * lp.cL - red[1] * lp.cL + red[2] * lp.cE - out[3] - out[4])
             terms = {'loglik': red[0], 'kl_x': red[1], 'entropy': red[2], 'kl_z_f': out[3], 'kl_z_b': out[4],
                      'info': out[7]}
         else:
@@ -211,6 +252,18 @@ class HipElboGrad:
                      'info': out[7]}
         self.last_ws = ws
         return loss, terms, ws
+
+    def _prepare(self, params, u, y, condition):
+        """inputs on the device, the problem, the flat / constrained parameters, and both GP packs prepared"""
+        cfg = self.config
+        u, y = _f64(u, self.device), _f64(y, self.device)
+        prob = _l.make_problem(u.shape[0], self.S, u.shape[1], self.dim_x, self.dim_u, self.dim_y, self.M,
+                               cfg['recog_len'], cfg['k_factor'], condition)
+        pflat = self._flat(params)
+        p, c = self._constrained_flat(pflat)
+        ops.prepare_pair(self.pack_f, (p['f.zeta_pos'], c['f.ls'], c['f.var'], p['f.zeta_mean'], c['f.zvar']),
+                         self.pack_b, (p['b.zeta_pos'], c['b.ls'], c['b.var'], p['b.zeta_mean'], c['b.zvar']))
+        return u, y, prob, pflat, p, c
 
     def _workspace(self, prob):
         key = (prob.B, prob.T)
@@ -232,16 +285,14 @@ class HipElboGrad:
                     assert na_f >= 0 and na_b > 0, 'record count'
                     reserve = 8.0 * prob.T * prob.B * prob.S * (3 * prob.dim_x + 8 * self.dob) + 2.0 * 2 ** 30
                     ws.a2s_f, ws.a2s_b = self.tile_pool.get(max(na_f, 1), na_b, reserve)
-                ws.gpart_f = torch.zeros((n_f + 32) * self.slab32_f, **f)
-                ws.gpart_b = torch.zeros((n_b + 32) * self.slab32_b, **f)
-                ws.n_f, ws.n_b = n_f, n_b
-                self._ws[key] = ws
-                return ws
-            if self.stash:
-                n_b = 2 * n_f          # one launch per segment range, grid.z = 1
-                ws.gx_carry = torch.zeros(prob.B * prob.S, prob.dim_x, **f)
-            ws.gpart_f = torch.zeros((n_f + 32) * self.slab_f, **f)      # + CBFSSM_REDUCE_SPLIT scratch slabs
-            ws.gpart_b = torch.zeros((n_b + 32) * self.slab_b, **f)
+                sf, sb = self.slab32_f, self.slab32_b
+            else:
+                if self.stash:
+                    n_b = 2 * n_f          # one launch per segment range, grid.z = 1
+                    ws.gx_carry = torch.zeros(prob.B * prob.S, prob.dim_x, **f)
+                sf, sb = self.slab_f, self.slab_b
+            ws.gpart_f = torch.zeros((n_f + 32) * sf, **f)      # + CBFSSM_REDUCE_SPLIT scratch slabs
+            ws.gpart_b = torch.zeros((n_b + 32) * sb, **f)
             ws.n_f, ws.n_b = n_f, n_b
             self._ws[key] = ws
         return self._ws[key]
@@ -266,58 +317,21 @@ class HipElboGrad:
 
     def _grads_local(self, params, u, y, noise, condition=True):
         self._need_adjoint()
-        lib = _l.load()
-        dev = self.device
-        cfg = self.config
-        u, y = _f64(u, dev), _f64(y, dev)
-        B, T = u.shape[0], u.shape[1]
-        prob = _l.make_problem(B, self.S, T, self.dim_x, self.dim_u, self.dim_y, self.M, cfg['recog_len'],
-                               cfg['k_factor'], condition)
-        pflat = self._flat(params)
-        p, c = self._constrained_flat(pflat)
-        ops.prepare_pair(self.pack_f, (p['f.zeta_pos'], c['f.ls'], c['f.var'], p['f.zeta_mean'], c['f.zvar']),
-                         self.pack_b, (p['b.zeta_pos'], c['b.ls'], c['b.var'], p['b.zeta_mean'], c['b.zvar']))
-        ws = self._workspace(prob)
-        self.last_ws = ws
-        hid_b, eps_b, eps_f = (_f64(noise[k], dev) for k in ('hid_b', 'eps_b', 'eps_f'))
-        lf = cfg['loss_factors']
-        self._elbo_forward(prob, ws, c, u, y, hid_b, eps_b, eps_f)
-
+        u, y, prob, pflat, p, c = self._prepare(params, u, y, condition)
+        self.last_ws = ws = self._workspace(prob)
+        lp = self._loops(prob, ws, c, u, y, noise)
+        self._elbo_forward(lp)
         # ---- adjoint time loops
-        st = _stream()
-        pb = C.byref(prob)
-        cL, cE = float(lf[0]) / self.S, float(lf[1]) / self.S
-        red = self.red
-        sf, sb = self.slab_f, self.slab_b
-        gB_f = gB_b = None
-        split = self._split(prob) if not self.f32 else self._split(prob, adjoint=False)
-        if self.f32:
-            gB_f, gB_b = self._adjoint_f32(prob, ws, c, u, y, hid_b, eps_b, eps_f, cL, cE, red, split)
-        elif not self.stash and split is not None:
-            self._adjoint_split(prob, split, ws, c, u, y, hid_b, eps_b, eps_f, cL, cE)
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), sf, ws.n_f, _ptr(red[:sf]), st), 'reduce f')
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_b), sb, ws.n_b, _ptr(red[sf:sf + sb]), st), 'reduce b')
-        elif not self.stash:
-            rc = lib.cbfssm_forward_pass_bwd_f64(pb, C.byref(self.pack_f.layout), _ptr(self.pack_f.buf),
-                                                 _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y), _ptr(ws.y2),
-                                                 _ptr(eps_f) if eps_f.numel() else None, _ptr(ws.x),
-                                                 _ptr(ws.fmv_f), _ptr(ws.a2s_f), cL, _ptr(ws.gy2),
-                                                 _ptr(ws.gpart_f), st)
-            _l.check(rc, 'cbfssm_forward_pass_bwd_f64')
-            rc = lib.cbfssm_backward_pass_bwd_f64(pb, C.byref(self.pack_b.layout), _ptr(self.pack_b.buf),
-                                                  _ptr(c['var_x']), _ptr(u), _ptr(y), _ptr(hid_b), _ptr(eps_b),
-                                                  _ptr(ws.h_all), _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.gy2), cE,
-                                                  _ptr(ws.gpart_b), st)
-            _l.check(rc, 'cbfssm_backward_pass_bwd_f64')
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), sf, ws.n_f, _ptr(red[:sf]), st), 'reduce f')
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_b), sb, ws.n_b, _ptr(red[sf:sf + sb]), st), 'reduce b')
+        if self.stash and not self.f32:
+            gB_f, gB_b = self._adjoint_stash(lp, self.red)
         else:
-            gB_f, gB_b = self._adjoint_stash(prob, ws, c, u, y, hid_b, eps_b, eps_f, cL, cE, red)
+            gB_f, gB_b = self._adjoint(lp, self.red)
         # ---- data scalars and the log-likelihood's pull on var_y (cbfssm.py:245-251)
-        tail = red[sf + sb:sf + sb + self.ntail]
-        _l.check(lib.cbfssm_data_tail_f64(pb, _ptr(c['var_y']), _ptr(ws.ll_part), _ptr(ws.out), cL, _ptr(tail), st),
-                 'cbfssm_data_tail_f64')
-        return dict(ws=ws, p=p, c=c, pflat=pflat, gB_f=gB_f, gB_b=gB_b, cL=cL, cE=cE)
+        sf, sb = self.slab_f, self.slab_b
+        tail = self.red[sf + sb:sf + sb + self.ntail]
+        _l.check(_l.load().cbfssm_data_tail_f64(C.byref(prob), _ptr(c['var_y']), _ptr(ws.ll_part), _ptr(ws.out), lp.cL,
+                                          _ptr(tail), _stream()), 'cbfssm_data_tail_f64')
+        return dict(ws=ws, p=p, c=c, pflat=pflat, gB_f=gB_f, gB_b=gB_b, cL=lp.cL, cE=lp.cE)
 
     def _grads_finish(self, s):
         lib = _l.load()
@@ -336,14 +350,10 @@ class HipElboGrad:
         terms = {'loglik': loglik, 'kl_x': kl_x, 'entropy': entropy, 'kl_z_f': kl_z_f, 'kl_z_b': kl_z_b,
                  'info': ws.out[7]}
         if self.fused_tail:
-            Mp = self.pack_f.layout.Mp
-            # float32 adjoint: the matrix section is G = K^-1 (d loss / d K^-1) K^-1 (full up to 10 row blocks, the
-            # lower-triangular blocks of G + G^T above: include/cbfssm_hip.h)
-            g_mode = 0 if not self.f32 else (2 if self.pack_f.layout.NBLK >= 13 else 1)
             rc = lib.cbfssm_train_tail_g_f64(C.byref(self.pl), C.byref(self.pack_f.layout), _ptr(self.pack_f.buf),
                                              C.byref(self.pack_b.layout), _ptr(self.pack_b.buf), _ptr(red), _ptr(gB_f),
-                                             _ptr(gB_b), 0, g_mode, _ptr(pflat), _ptr(self.cflat), _ptr(self.tail_work),
-                                             _ptr(self.gflat), st)
+                                             _ptr(gB_b), 0, g_mode(self.f32, self.pack_f.layout), _ptr(pflat),
+                                             _ptr(self.cflat), _ptr(self.tail_work), _ptr(self.gflat), st)
             _l.check(rc, 'cbfssm_train_tail_g_f64')
             return loss, _flat_views(self.gflat, self.pl, self.dim_u), terms
 
@@ -352,27 +362,11 @@ class HipElboGrad:
         gvx = torch.zeros(self.dim_x, dtype=torch.float64, device=dev)
         gvy = torch.zeros(self.dim_x, dtype=torch.float64, device=dev)
         if self.f32:
-            # the float32 adjoint's matrix section holds G = K^-1 (d loss / d K^-1) K^-1 (include/cbfssm_hip.h); this
-            # restatement expects d loss / d K^-1 = K G K, K = K_mm + jitter I
-            def kinv_adjoint(img, pack):
-                nb, M = pack.layout.NBLK, pack.M
-                G = _unpack_c(img, nb, nb)
-                if nb >= 13:             # lower-triangular blocks of G + G^T (diagonal blocks: of G)
-                    blk = torch.arange(16 * nb, device=dev) // 16
-                    G = torch.where(blk[:, None] >= blk[None, :], G, torch.zeros_like(G))
-                G = 0.5 * (G + G.T)[:M, :M]
-                K = pack.Kmm + pack.scal[_l.SCAL_JITTER] * torch.eye(M, dtype=torch.float64, device=dev)
-                Bd = torch.zeros(16 * nb, 16 * nb, dtype=torch.float64, device=dev)
-                Bd[:M, :M] = K @ G @ K
-                return Bd.view(nb, 4, 4, nb, 16).permute(0, 3, 1, 2, 4).reshape(-1)
-            nbf, nbb = self.pack_f.layout.NBLK, self.pack_b.layout.NBLK
-            gB_f = kinv_adjoint(gB_f if gB_f is not None else red[2 * nbf * 256:2 * nbf * 256 + nbf * nbf * 256], self.pack_f)
-            gB_b = kinv_adjoint(gB_b if gB_b is not None else red[sf + 2 * nbb * 256:sf + 2 * nbb * 256 + nbb * nbb * 256],
-                                self.pack_b)
+            gB_f, gB_b = kgk_image(self.pack_f, red[:sf], gB_f), kgk_image(self.pack_b, red[sf:sf + sb], gB_b)
         for g, pack, slab, Do, gBx in (('f', self.pack_f, red[:sf], self.dim_x, gB_f),
                                        ('b', self.pack_b, red[sf:sf + sb], self.dob, gB_b)):
-            gz, gmu, gs2, gvar, gls, small = self._gp_adjoint(pack, slab, p[g + '.zeta_pos'], c[g + '.ls'], c[g + '.var'],
-                                                              p[g + '.zeta_mean'], c[g + '.zvar'], Do, gBx)
+            gz, gmu, gs2, gvar, gls, small = _gp_adjoint(pack, slab, p[g + '.zeta_pos'], c[g + '.ls'], c[g + '.var'],
+                                                         p[g + '.zeta_mean'], c[g + '.zvar'], Do, not self.stash, gBx)
             grads[g + '.zeta_pos'] = gz
             grads[g + '.zeta_mean'] = gmu
             grads[g + '.zeta_var_unc'] = gs2 * torch.sigmoid(p[g + '.zeta_var_unc'])
@@ -416,162 +410,81 @@ class HipElboGrad:
             self._s1 = torch.cuda.Stream(device=self.device)
         return self._s1
 
-    def _elbo_forward(self, prob, ws, c, u, y, hid_b, eps_b, eps_f):
+    def _loops(self, prob, ws, c, u, y, noise):
+        """the time-loop entry points bound to this evaluation's operands"""
+        hid_b, eps_b, eps_f = (_f64(noise[k], self.device) for k in ('hid_b', 'eps_b', 'eps_f'))
         lf = self.config['loss_factors']
-        split = self._split(prob, adjoint=False)
-        if split is None:
-            ops.elbo_forward(prob, self.pack_f, self.pack_b, c['var_x'], c['var_y'], u, y, hid_b, eps_b, eps_f, lf, ws,
-                             f32=self.f32)
-            return
-        lib = _l.load()
+        return ops.TimeLoops(prob, ws, self.pack_f, self.pack_b, c['var_x'], c['var_y'], u, y, eps_f, hid_b, eps_b,
+                             cL=float(lf[0]) / self.S, cE=float(lf[1]) / self.S, f32=self.f32)
+
+    def _two_streams(self, prob, split):
+        """(main piece, remainder piece, current stream, side stream, their handles)"""
         main, rest = split
-        p_main, p_rest = self._sub_problem(prob, 0, main), self._sub_problem(prob, main, rest)
         s0, s1 = torch.cuda.current_stream(), self._side_stream()
-        st0, st1 = C.c_void_p(s0.cuda_stream), C.c_void_p(s1.cuda_stream)
-        lb, lf_ = C.byref(self.pack_b.layout), C.byref(self.pack_f.layout)
-        e_eps = _ptr(eps_f) if eps_f.numel() else None
+        return (self._sub_problem(prob, 0, main), self._sub_problem(prob, main, rest), s0, s1,
+                C.c_void_p(s0.cuda_stream), C.c_void_p(s1.cuda_stream))
 
-        if self.f32:
-            b32b, b32f = (C.c_void_p(pk.pack_f32().data_ptr()) for pk in (self.pack_b, self.pack_f))   # (re-packed on s0)
-
-        def bwd(q, st):
-            if self.f32:
-                _l.check(lib.cbfssm_backward_pass_f32(C.byref(q), lb, b32b, _ptr(c['var_x']), _ptr(u), _ptr(y), _ptr(hid_b),
-                                                      _ptr(eps_b), _ptr(ws.y2), _ptr(ws.h_all), _ptr(ws.fmv_b),
-                                                      _ptr(ws.a2s_b), _ptr(ws.ent_part), st), 'cbfssm_backward_pass_f32')
-                return
-            _l.check(lib.cbfssm_backward_pass_f64(C.byref(q), lb, _ptr(self.pack_b.buf), _ptr(c['var_x']), _ptr(u), _ptr(y),
-                                                  _ptr(hid_b), _ptr(eps_b), _ptr(ws.y2), _ptr(ws.h_all),
-                                                  _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.ent_part), st),
-                     'cbfssm_backward_pass_f64')
-
-        def fwd(q, st):
-            if self.f32:
-                _l.check(lib.cbfssm_forward_pass_f32(C.byref(q), lf_, b32f, _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y),
-                                                     _ptr(ws.y2), e_eps, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f),
-                                                     _ptr(ws.kl_part), st),
-                         'cbfssm_forward_pass_f32')
-                return
-            _l.check(lib.cbfssm_forward_pass_f64(C.byref(q), lf_, _ptr(self.pack_f.buf), _ptr(c['var_x']), _ptr(c['var_y']),
-                                                 _ptr(u), _ptr(y), _ptr(ws.y2), e_eps, _ptr(ws.x), _ptr(ws.fmv_f),
-                                                 _ptr(ws.a2s_f), _ptr(ws.kl_part), st), 'cbfssm_forward_pass_f64')
+    def _elbo_forward(self, lp):
+        lf = self.config['loss_factors']
+        split = self._split(lp.prob, adjoint=False)
+        if split is None:
+            ops.elbo_forward(lp, lf)
+            return
+        p_main, p_rest, s0, s1, st0, st1 = self._two_streams(lp.prob, split)
+        lp.cast_f32()                          # (on s0)
         e0 = torch.cuda.Event()
         e0.record(s0)
-        bwd(p_rest, st0)                       # the remainder groups first ...
-        fwd(p_rest, st0)                       # ... their (few, long) forward workgroups overlap
+        lp.backward_pass(p_rest, st0)          # the remainder groups first ...
+        lp.forward_pass(p_rest, st0)           # ... their (few, long) forward workgroups overlap
         s1.wait_event(e0)
-        bwd(p_main, st1)                       # ... the many short backward-run workgroups of the main piece
+        lp.backward_pass(p_main, st1)          # ... the many short backward-run workgroups of the main piece
         e1 = torch.cuda.Event()
         e1.record(s1)
         s0.wait_event(e1)
-        fwd(p_main, st0)
-        pb = C.byref(prob)
-        rc = lib.cbfssm_loglik_moments_f64(pb, _ptr(c['var_y']), _ptr(y), _ptr(ws.x), _ptr(ws.ll_part),
-                                           _ptr(ws.pred_mean), _ptr(ws.pred_var), _ptr(ws.int_mean), _ptr(ws.int_var), st0)
-        _l.check(rc, 'cbfssm_loglik_moments_f64')
-        rc = lib.cbfssm_elbo_combine_f64(pb, float(lf[0]), float(lf[1]), _ptr(ws.ll_part), ws.ll_part.numel(),
-                                         _ptr(ws.kl_part), ws.kl_part.numel(), _ptr(ws.ent_part), ws.ent_part.numel(),
-                                         _ptr(self.pack_f.scal), _ptr(self.pack_b.scal), _ptr(ws.out), st0)
-        _l.check(rc, 'cbfssm_elbo_combine_f64')
+        lp.forward_pass(p_main, st0)
+        lp.elbo_tail(lf[0], lf[1], st0)
 
-    def _adjoint_split(self, prob, split, ws, c, u, y, hid_b, eps_b, eps_f, cL, cE):
-        lib = _l.load()
-        main, rest = split
-        p_main, p_rest = self._sub_problem(prob, 0, main), self._sub_problem(prob, main, rest)
-        s0, s1 = torch.cuda.current_stream(), self._side_stream()
-        st0, st1 = C.c_void_p(s0.cuda_stream), C.c_void_p(s1.cuda_stream)
-        lb, lf_ = C.byref(self.pack_b.layout), C.byref(self.pack_f.layout)
-        e_eps = _ptr(eps_f) if eps_f.numel() else None
-
-        def rfwd(q, st):
-            _l.check(lib.cbfssm_forward_pass_bwd_f64(C.byref(q), lf_, _ptr(self.pack_f.buf), _ptr(c['var_x']),
-                                                     _ptr(c['var_y']), _ptr(u), _ptr(y), _ptr(ws.y2), e_eps, _ptr(ws.x),
-                                                     _ptr(ws.fmv_f), _ptr(ws.a2s_f), cL, _ptr(ws.gy2), _ptr(ws.gpart_f), st), 'cbfssm_forward_pass_bwd_f64')
-
-        def rbwd(q, st):
-            _l.check(lib.cbfssm_backward_pass_bwd_f64(C.byref(q), lb, _ptr(self.pack_b.buf), _ptr(c['var_x']), _ptr(u),
-                                                      _ptr(y), _ptr(hid_b), _ptr(eps_b), _ptr(ws.h_all), _ptr(ws.fmv_b),
-                                                      _ptr(ws.a2s_b), _ptr(ws.gy2), cE, _ptr(ws.gpart_b), st),
-                     'cbfssm_backward_pass_bwd_f64')
-        rfwd(p_main, st0)                      # a whole number of rounds over the CUs
-        e2 = torch.cuda.Event()
-        e2.record(s0)
-        rfwd(p_rest, st0)                      # few long workgroups ...
-        s1.wait_event(e2)
-        rbwd(p_main, st1)                      # ... next to the main piece's backward-run adjoint
-        e3 = torch.cuda.Event()
-        e3.record(s1)
-        rbwd(p_rest, st0)
-        s0.wait_event(e3)
-
-    def _adjoint_f32(self, prob, ws, c, u, y, hid_b, eps_b, eps_f, cL, cE, red, split=None):
-        """float32 adjoint (cbfssm_*_pass_bwd_f32): one call per direction (above 208 inducing points a call is two passes
-        over the time loop), float64 slabs in the non-stash layout reduced by the float64 reduction.  For the tile heights
-        whose float64 adjoint runs in stash mode the Kinvbar section of the reduced slab is handed to the train tail the
-        way the stash contraction's images are."""
-        lib = _l.load()
-        pb = C.byref(prob)
-        st = _stream()
-        b32f, b32b = self.pack_f.buf32, self.pack_b.buf32           # filled by the forward evaluation (ops.elbo_forward)
+    def _adjoint(self, lp, red):
+        """Adjoint below the stash tile heights (cbfssm_*_pass_bwd_f64) and the float32 one at every height
+        (cbfssm_*_pass_bwd_f32: above 208 inducing points a call is two passes over the time loop), one launch per
+        direction or in the chain-group split, reduced into `red`.  Returns the K^-1-adjoint images of the float32
+        re-pack (repack_f32), or (None, None)."""
+        ws, st = lp.ws, _stream()
         sf, sb = self.slab_f, self.slab_b
-        e_eps = _ptr(eps_f) if eps_f.numel() else None
-
-        def rfwd(q, stq):
-            _l.check(lib.cbfssm_forward_pass_bwd_f32(C.byref(q), C.byref(self.pack_f.layout), C.c_void_p(b32f.data_ptr()),
-                                                     _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y), _ptr(ws.y2), e_eps,
-                                                     _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), cL, _ptr(ws.gy2), _ptr(ws.gpart_f), stq),
-                     'cbfssm_forward_pass_bwd_f32')
-
-        def rbwd(q, stq):
-            _l.check(lib.cbfssm_backward_pass_bwd_f32(C.byref(q), C.byref(self.pack_b.layout), C.c_void_p(b32b.data_ptr()),
-                                                      _ptr(c['var_x']), _ptr(u), _ptr(y), _ptr(hid_b), _ptr(eps_b),
-                                                      _ptr(ws.h_all), _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.gy2), cE, _ptr(ws.gpart_b), stq),
-                     'cbfssm_backward_pass_bwd_f32')
+        # (the stash-mode schedule that _split leaves out for the adjoint is the float64 one, which does not come here)
+        split = self._split(lp.prob, adjoint=False)
         if split is None:
-            rfwd(prob, st)
-            rbwd(prob, st)
+            lp.forward_pass_bwd(lp.prob, st)
+            lp.backward_pass_bwd(lp.prob, st)
         else:
-            # the chain-group split of the float64 adjoint (_adjoint_split): a main piece of whole rounds over the CUs, the
-            # remainder's forward-pass adjoint next to the main piece's many-workgroup backward-run adjoint
-            main, rest = split
-            p_main, p_rest = self._sub_problem(prob, 0, main), self._sub_problem(prob, main, rest)
-            s0, s1 = torch.cuda.current_stream(), self._side_stream()
-            st0, st1 = C.c_void_p(s0.cuda_stream), C.c_void_p(s1.cuda_stream)
-            rfwd(p_main, st0)
+            p_main, p_rest, s0, s1, st0, st1 = self._two_streams(lp.prob, split)
+            lp.forward_pass_bwd(p_main, st0)       # a whole number of rounds over the CUs
             e2 = torch.cuda.Event()
             e2.record(s0)
-            rfwd(p_rest, st0)
+            lp.forward_pass_bwd(p_rest, st0)       # few long workgroups ...
             s1.wait_event(e2)
-            rbwd(p_main, st1)
+            lp.backward_pass_bwd(p_main, st1)      # ... next to the main piece's backward-run adjoint
             e3 = torch.cuda.Event()
             e3.record(s1)
-            rbwd(p_rest, st0)
+            lp.backward_pass_bwd(p_rest, st0)
             s0.wait_event(e3)
-        if not self.stash:
-            assert self.slab32_f == sf and self.slab32_b == sb
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), sf, ws.n_f, _ptr(red[:sf]), st), 'reduce f')
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_b), sb, ws.n_b, _ptr(red[sf:sf + sb]), st), 'reduce b')
-            # (the matrix section holds G = K^-1 (d loss / d K^-1) K^-1, the data part of d loss / d K_mm itself:
-            #  cbfssm_train_tail_g_f64 takes it as it is, _grads_finish passes g_mode)
+        if not self.repack32:
+            assert not self.f32 or (self.slab32_f, self.slab32_b) == (sf, sb)
+            ops.reduce_partials(ws.gpart_f, sf, ws.n_f, red[:sf], st)
+            ops.reduce_partials(ws.gpart_b, sb, ws.n_b, red[sf:sf + sb], st)
             return None, None
-        if getattr(self, '_tmp32', None) is None:
+        if self._tmp32 is None:
             self._tmp32 = torch.zeros(self.slab32_f + self.slab32_b, dtype=torch.float64, device=self.device)
         tf, tb = self._tmp32[:self.slab32_f], self._tmp32[self.slab32_f:]
-        _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), self.slab32_f, ws.n_f, _ptr(tf), st), 'reduce f')
-        _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_b), self.slab32_b, ws.n_b, _ptr(tb), st), 'reduce b')
+        ops.reduce_partials(ws.gpart_f, self.slab32_f, ws.n_f, tf, st)
+        ops.reduce_partials(ws.gpart_b, self.slab32_b, ws.n_b, tb, st)
         o = self.nred
-        imgs = []
-        for t32, lo, n, nimg, io in ((tf, 0, sf, self.nimg_f, o), (tb, sf, sb, self.nimg_b, o + self.nimg_f)):
-            nb = int(round((nimg // 256) ** 0.5))
-            og = 2 * nb * 256                                        # [mubar | s2bar] precede the Kinvbar images
-            red[lo:lo + og].copy_(t32[:og])
-            red[lo + og:lo + n].copy_(t32[og + nimg:])
-            img = red[io:io + nimg]
-            img.copy_(t32[og:og + nimg])
-            imgs.append(img)
-        return imgs[0], imgs[1]
+        img_f, img_b = red[o:o + self.nimg_f], red[o + self.nimg_f:o + self.nimg_f + self.nimg_b]
+        repack_f32(tf, red[:sf], img_f, self.pack_f.layout.NBLK)
+        repack_f32(tb, red[sf:sf + sb], img_b, self.pack_b.layout.NBLK)
+        return img_f, img_b
 
-    def _adjoint_stash(self, prob, ws, c, u, y, hid_b, eps_b, eps_f, cL, cE, red):
+    def _adjoint_stash(self, lp, red):
         """Stash-mode adjoint (M > 112): time-chunked launches, every launch followed by one float64 GEMM that
         contracts the stashed A2bar / K tiles into d loss / d K^-1 (include/cbfssm_hip.h).
 
@@ -579,8 +492,7 @@ class HipElboGrad:
         (a range of resample-to-resample segments of both runs) needs the y2 adjoint only for its own time range, so it
         starts on the side stream as soon as the forward-pass adjoint has passed below that range and fills the CUs the
         one-workgroup-per-chain-group forward-pass adjoint leaves idle (320 workgroups on 256 CUs at C4)."""
-        lib = _l.load()
-        pb = C.byref(prob)
+        prob, ws = lp.prob, lp.ws
         dev = self.device
         f = dict(dtype=torch.float64, device=dev)
         Mp = self.pack_f.layout.Mp
@@ -596,7 +508,7 @@ class HipElboGrad:
                                torch.zeros(Mp * cols_b, **f), torch.zeros(Mp * cols_b, **f))
         sa_f, sk_f, sa_b, sk_b = self._stash_buf
         sf, sb = self.slab_f, self.slab_b
-        nseg = int(lib.cbfssm_bwd_segments(pb))
+        nseg = int(_l.load().cbfssm_bwd_segments(C.byref(prob)))
         per_b = max(1, cols_b // (groups * 2 * P * 16))
         # measurement hook (bench.py): with a list in self._prof every launch of this schedule is bracketed by HIP events on
         # ONE stream (no overlap between the two directions), so that each kernel's own time can be summed per kind
@@ -614,18 +526,8 @@ class HipElboGrad:
         con_f, con_b = self._contract
         con_f.image.zero_()
         con_b.image.zero_()
-        e_eps = _ptr(eps_f) if eps_f.numel() else None
         if overlap:
             s1.wait_stream(s0)                               # the forward evaluation and the zeroing above
-
-        def timed(kind, stream, fn):
-            if prof is None:
-                return fn()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            prof.append((kind, e0, e1))
 
         def rfwd(t_hi, t_lo):
             """forward-pass adjoint of steps t_hi .. t_lo (descending) in launches that fit the stash, on s0"""
@@ -633,19 +535,17 @@ class HipElboGrad:
             while True:
                 lo = max(t_lo, t_hi - per + 1)
                 cols = groups * max(0, t_hi - lo + 1) * 16
-                timed('forward_pass_adjoint', s0, lambda: _l.check(lib.cbfssm_forward_pass_bwd_ex_f64(
-                    pb, C.byref(self.pack_f.layout), _ptr(self.pack_f.buf), _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y),
-                    _ptr(ws.y2), e_eps, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), cL, _ptr(ws.gy2), _ptr(ws.gpart_f), t_hi, lo,
-                    _ptr(ws.gx_carry), _ptr(sa_f), _ptr(sk_f), cols, st0), 'cbfssm_forward_pass_bwd_ex_f64'))
+                _timed(prof, 'forward_pass_adjoint', s0,
+                       lambda: lp.forward_pass_bwd(prob, st0, (t_hi, lo, sa_f, sk_f, cols)))
                 ev = torch.cuda.Event()
                 ev.record(s0)                                # gy2[t] is final for every t > lo (and t = 0 once lo = 0)
 
                 def red_f():
-                    _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), sf, groups, _ptr(tmp_f[:sf]), st0), 'reduce f')
+                    ops.reduce_partials(ws.gpart_f, sf, groups, tmp_f[:sf], st0)
                     red[:sf] += tmp_f[:sf]
-                timed('reductions', s0, red_f)
+                _timed(prof, 'reductions', s0, red_f)
                 if cols:
-                    timed('stash_contraction', s0, lambda: con_f.add(sa_f, sk_f, cols, st0))
+                    _timed(prof, 'stash_contraction', s0, lambda: con_f.add(sa_f, sk_f, cols, st0))
                 if lo <= t_lo or t_hi < 0:
                     return ev
                 t_hi = lo - 1
@@ -654,16 +554,14 @@ class HipElboGrad:
             """both backward runs, segments [seg0, seg1), on s1"""
             cols = groups * 2 * (seg1 - seg0) * P * 16
             with torch.cuda.stream(s1):
-                timed('backward_pass_adjoint', s1, lambda: _l.check(lib.cbfssm_backward_pass_bwd_ex_f64(
-                    pb, C.byref(self.pack_b.layout), _ptr(self.pack_b.buf), _ptr(c['var_x']), _ptr(u), _ptr(y), _ptr(hid_b),
-                    _ptr(eps_b), _ptr(ws.h_all), _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.gy2), cE, _ptr(ws.gpart_b), seg0, seg1, 1,
-                    _ptr(sa_b), _ptr(sk_b), cols, st1), 'cbfssm_backward_pass_bwd_ex_f64'))
+                _timed(prof, 'backward_pass_adjoint', s1,
+                       lambda: lp.backward_pass_bwd(prob, st1, (seg0, seg1, sa_b, sk_b, cols)))
 
                 def red_b():
-                    _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_b), sb, 2 * groups, _ptr(tmp_b[:sb]), st1), 'reduce b')
+                    ops.reduce_partials(ws.gpart_b, sb, 2 * groups, tmp_b[:sb], st1)
                     red[sf:sf + sb] += tmp_b[:sb]
-                timed('reductions', s1, red_b)
-                timed('stash_contraction', s1, lambda: con_b.add(sa_b, sk_b, cols, st1))
+                _timed(prof, 'reductions', s1, red_b)
+                _timed(prof, 'stash_contraction', s1, lambda: con_b.add(sa_b, sk_b, cols, st1))
 
         t_hi = T - 2                                         # next forward-pass-adjoint step to process
         seg1 = nseg
@@ -690,59 +588,61 @@ class HipElboGrad:
             s0.wait_stream(s1)
         return con_f.image, con_b.image
 
-    def _gp_adjoint(self, pack, slab, Z, ls, var, zmean, zvar, Do, gB_stash=None, kl_pack=None):
-        """Adjoint of gp_prepare (K_mm -> chol -> K^-1, operand scaling, prior KL) given the reduced data slab."""
-        lay = pack.layout
-        M, D, NBLK, JB = self.M, self.D, lay.NBLK, lay.JB
-        o = 0
-        gmu = _unpack_c(slab[o:o + NBLK * 256], NBLK, 1)[:M, :Do]
-        o += NBLK * 256
-        gs2 = _unpack_c(slab[o:o + NBLK * 256], NBLK, 1)[:M, :Do]
-        o += NBLK * 256
-        if gB_stash is None:
-            gB = _unpack_c(slab[o:o + NBLK * NBLK * 256], NBLK, NBLK)[:M, :M]
-        else:
-            gB = _unpack_c(gB_stash, NBLK, NBLK)[:M, :M]           # C-layout image of cbfssm_stash_contract_f64
-        if not self.stash:
-            o += NBLK * NBLK * 256                                 # (the slab of a non-stash tile height has the section)
-        gZf = _unpack_c(slab[o:o + NBLK * JB * 256], NBLK, JB)
-        o += NBLK * JB * 256
-        small = slab[o:o + 128]
-        Kinv, Kmm = pack.Kinv, pack.Kmm
-        Zs = pack.section('Zs', (M, D))
-        gZt = gZf[:M, :D] - Zs * gZf[:M, D:D + 1]           # Ebar x~^T - z~ o rowsum(Ebar)
-        glx = small[32:32 + D]
-        gsig, glogsig = small[96], small[97]
-        # prior KL (gp_tf.py:163-172), weight 1 in the loss, added once (rank invariant).  PR-SSM factorises the prior
-        # without jitter (prssm.py:81-82): its KL terms then use the jitter-free inverse of kl_pack.
-        Kkl = kl_pack.Kinv if kl_pack is not None else Kinv
-        gmu = gmu + Kkl @ zmean
-        gs2 = gs2 + 0.5 * (torch.diagonal(Kkl)[:, None] - 1.0 / zvar)
-        gB_kl = 0.5 * (torch.diag(zvar.sum(1)) + zmean @ zmean.T)
-        # K^-1 = (K_mm + jitter I)^-1 ; log det term of the KL: d/dK (0.5 Do log det K) = 0.5 Do K^-1
-        jit = pack.scal[_l.SCAL_JITTER]
-        if kl_pack is None:
-            T = Kinv @ (gB + gB_kl)
-            TK = T @ Kinv
-            gK = -TK + 0.5 * Do * Kinv
-            # tr(Kbar K_mm) with K^-1 K_mm = I - jitter K^-1: the terms are of order cond |G|, where the entry sum of
-            # Kbar o K_mm cancels numbers of order cond^2 |G| (it decides d loss / d sigma^2 on an ill-conditioned K_mm)
-            tr_gKK = -torch.trace(T) + jit * torch.trace(TK) + 0.5 * Do * (M - jit * torch.trace(Kinv))
-        else:
-            T = Kinv @ gB
-            TK = T @ Kinv
-            gK = -TK - (Kkl @ gB_kl @ Kkl) + 0.5 * Do * Kkl
-            # (the prior's K_kl^-1 is jitter free: K_kl^-1 K_mm = I)
-            tr_gKK = -torch.trace(T) + jit * torch.trace(TK) - (Kkl * gB_kl.T).sum() + 0.5 * Do * M
-        # K = var * exp(-0.5 d2(z~))                                           (gp_tf.py:33-49)
-        gKK = gK * Kmm
-        gvar = tr_gKK / var[0] + gsig + glogsig / var[0]
-        Wd = -0.5 * gKK
-        Ws = Wd + Wd.T
-        gZt = gZt + 2.0 * (Ws.sum(1)[:, None] * Zs - Ws @ Zs)
-        gz = gZt / ls
-        gls = -((gZt * Zs).sum(0) + glx) / ls
-        return gz, gmu, gs2, gvar, gls, small
+
+def _gp_adjoint(pack, slab, Z, ls, var, zmean, zvar, Do, kinv_section, gB_stash=None, kl_pack=None):
+    """Adjoint of gp_prepare (K_mm -> chol -> K^-1, operand scaling, prior KL) given the reduced data slab;
+    kinv_section: the slab has the matrix section (below the stash tile heights)."""
+    lay = pack.layout
+    M, D, NBLK, JB = pack.M, pack.D, lay.NBLK, lay.JB
+    o = 0
+    gmu = _unpack_c(slab[o:o + NBLK * 256], NBLK, 1)[:M, :Do]
+    o += NBLK * 256
+    gs2 = _unpack_c(slab[o:o + NBLK * 256], NBLK, 1)[:M, :Do]
+    o += NBLK * 256
+    if gB_stash is None:
+        gB = _unpack_c(slab[o:o + NBLK * NBLK * 256], NBLK, NBLK)[:M, :M]
+    else:
+        gB = _unpack_c(gB_stash, NBLK, NBLK)[:M, :M]           # C-layout image of cbfssm_stash_contract_f64
+    if kinv_section:
+        o += NBLK * NBLK * 256
+    gZf = _unpack_c(slab[o:o + NBLK * JB * 256], NBLK, JB)
+    o += NBLK * JB * 256
+    small = slab[o:o + 128]
+    Kinv, Kmm = pack.Kinv, pack.Kmm
+    Zs = pack.section('Zs', (M, D))
+    gZt = gZf[:M, :D] - Zs * gZf[:M, D:D + 1]           # Ebar x~^T - z~ o rowsum(Ebar)
+    glx = small[32:32 + D]
+    gsig, glogsig = small[96], small[97]
+    # prior KL (gp_tf.py:163-172), weight 1 in the loss, added once (rank invariant).  PR-SSM factorises the prior
+    # without jitter (prssm.py:81-82): its KL terms then use the jitter-free inverse of kl_pack.
+    Kkl = kl_pack.Kinv if kl_pack is not None else Kinv
+    gmu = gmu + Kkl @ zmean
+    gs2 = gs2 + 0.5 * (torch.diagonal(Kkl)[:, None] - 1.0 / zvar)
+    gB_kl = 0.5 * (torch.diag(zvar.sum(1)) + zmean @ zmean.T)
+    # K^-1 = (K_mm + jitter I)^-1 ; log det term of the KL: d/dK (0.5 Do log det K) = 0.5 Do K^-1
+    jit = pack.scal[_l.SCAL_JITTER]
+    if kl_pack is None:
+        T = Kinv @ (gB + gB_kl)
+        TK = T @ Kinv
+        gK = -TK + 0.5 * Do * Kinv
+        # tr(Kbar K_mm) with K^-1 K_mm = I - jitter K^-1: the terms are of order cond |G|, where the entry sum of
+        # Kbar o K_mm cancels numbers of order cond^2 |G| (it decides d loss / d sigma^2 on an ill-conditioned K_mm)
+        tr_gKK = -torch.trace(T) + jit * torch.trace(TK) + 0.5 * Do * (M - jit * torch.trace(Kinv))
+    else:
+        T = Kinv @ gB
+        TK = T @ Kinv
+        gK = -TK - (Kkl @ gB_kl @ Kkl) + 0.5 * Do * Kkl
+        # (the prior's K_kl^-1 is jitter free: K_kl^-1 K_mm = I)
+        tr_gKK = -torch.trace(T) + jit * torch.trace(TK) - (Kkl * gB_kl.T).sum() + 0.5 * Do * M
+    # K = var * exp(-0.5 d2(z~))                                           (gp_tf.py:33-49)
+    gKK = gK * Kmm
+    gvar = tr_gKK / var[0] + gsig + glogsig / var[0]
+    Wd = -0.5 * gKK
+    Ws = Wd + Wd.T
+    gZt = gZt + 2.0 * (Ws.sum(1)[:, None] * Zs - Ws @ Zs)
+    gz = gZt / ls
+    gls = -((gZt * Zs).sum(0) + glx) / ls
+    return gz, gmu, gs2, gvar, gls, small
 
 
 class TFAdam:
@@ -838,6 +738,8 @@ class HipTrainStep:
         if graph is None:
             graph = config.get('hip_graph', os.environ.get('CBFSSM_HIP_GRAPH', '1') != '0')
         # With a process group the collective stays eager between two graphs (local part / tail + Adam).
+        # (`stash` is the float64 layout's flag: float32 engines at those tile heights run eagerly too, although their
+        #  adjoint is one launch per direction.  Letting them capture changes speed: a change of its own)
         self.use_graph = bool(graph) and not self.engine.stash
         self._graphs = {}
         self.last_ws = None

@@ -16,7 +16,7 @@ from . import lib as _l
 from . import ops
 from .ops import _ptr, _stream, _f64, tf_forward, GPPack
 from .dist_utils import all_reduce_sum
-from .train import HipElboGrad, LOG2PI, StashContract, FlatDict
+from .train import StashContract, FlatDict, _gp_adjoint, _timed, repacks_f32, repack_f32, g_mode, kgk_image
 
 GP_NAMES = ('f.zeta_pos', 'f.zeta_mean', 'f.zeta_var_unc', 'f.variance_unc', 'f.lengthscales_unc')
 RECOG_NAMES = ('recog.gate_kernel', 'recog.gate_bias', 'recog.cand_kernel', 'recog.cand_bias', 'recog.dense_kernel',
@@ -100,14 +100,15 @@ class HipHalfGrad:
             # per-workgroup slabs of the float32 adjoint: the non-stash layout at every tile height (matrix section included)
             self.slab32_f = int(_l.load().cbfssm_rev32_slab_elems(C.byref(self.pack_f.layout)))
         self.stash = bool(self.pack_f.layout.rev_stash)
+        self.repack32 = repacks_f32(self.f32, self.pack_f.layout)
+        self._tmp32 = None
         self.stash_bytes = int(float(config.get('adjoint_stash_gib', 4.0)) * 2 ** 30)
         self._stash_buf = None
         self.slab_f = int(self.pack_f.layout.rev_slab)
         self._ws = {}
         self.last_ws = None
         # the K_mm / Cholesky / prior-KL adjoint is shared with CBFSSM: cbfssm_train_tail_half_f64 (five launches on flat
-        # vectors); CBFSSM_TORCH_TAIL=1 keeps the tensor-library restatement (same numbers, a cross-check)
-        self._gp_adjoint = HipElboGrad._gp_adjoint.__get__(self)
+        # vectors); CBFSSM_TORCH_TAIL=1 keeps the tensor-library restatement (train._gp_adjoint: same numbers, a cross-check)
         self.fused_tail = self.slab_f > 0 and not os.environ.get('CBFSSM_TORCH_TAIL')
         self.gp_names = self.names[:7]                       # the five GP tensors, var_x_unc, var_y_unc: the tail's flat order
         self.tail_work = None
@@ -115,18 +116,6 @@ class HipHalfGrad:
         # library launches through autograd; CBFSSM_TORCH_GRU=1 keeps the latter (same numbers, a cross-check)
         self.fused_gru = self.rnn and not os.environ.get('CBFSSM_TORCH_GRU')
         self._gru = {}
-
-    def _timed(self, kind, fn):
-        """measurement hook (bench.py --model half|prssm): with a list in self._prof the launch is bracketed by HIP events"""
-        prof = getattr(self, '_prof', None)
-        if prof is None:
-            return fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = fn()
-        e1.record()
-        prof.append((kind, e0, e1))
-        return rc
 
     def _problem(self, B, T, condition):
         c = self.config
@@ -178,33 +167,20 @@ class HipHalfGrad:
         B = u.shape[0]
         return torch.cat((y[:, 0, :], torch.zeros(B, self.dim_x - self.dim_y, dtype=u.dtype, device=u.device)), dim=1)
 
-    def _forward(self, p, c, x0, u, y, eps_f, prob, ws):
-        lib = _l.load()
+    def _loops(self, prob, ws, c, u, y, x0, eps_f):
+        """the time-loop entry points bound to this evaluation's operands"""
+        return ops.TimeLoops(prob, ws, self.pack_f, None, c['var_x'], c['var_y'], u, y, eps_f, x0=x0, cL=self.cL,
+                             f32=self.f32)
+
+    def _forward(self, lp, p, c):
         st = _stream()
-        pb = C.byref(prob)
         pre = self.pre
         self.pack_f.prepare(p[pre + 'zeta_pos'], c['ls'], c['var'], p[pre + 'zeta_mean'], c['zvar'])
         if self.pack_kl is not None:
             self.pack_kl.prepare(p[pre + 'zeta_pos'], c['ls'], c['var'], p[pre + 'zeta_mean'], c['zvar'], jitter=0.0)
-        lay = C.byref(self.pack_f.layout)
-        if self.f32:
-            b32 = C.c_void_p(self.pack_f.pack_f32().data_ptr())
-            rc = self._timed('forward_pass', lambda: lib.cbfssm_half_forward_pass_f32(
-                pb, lay, b32, _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y), _ptr(x0),
-                _ptr(eps_f) if eps_f.numel() else None, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), _ptr(ws.kl_part), st))
-            _l.check(rc, 'cbfssm_half_forward_pass_f32')
-        else:
-            rc = self._timed('forward_pass', lambda: lib.cbfssm_half_forward_pass_f64(
-                pb, lay, _ptr(self.pack_f.buf), _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y), _ptr(x0),
-                _ptr(eps_f) if eps_f.numel() else None, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), _ptr(ws.kl_part), st))
-            _l.check(rc, 'cbfssm_half_forward_pass_f64')
-        rc = lib.cbfssm_loglik_moments_f64(pb, _ptr(c['var_y']), _ptr(y), _ptr(ws.x), _ptr(ws.ll_part),
-                                           _ptr(ws.pred_mean), _ptr(ws.pred_var), _ptr(ws.int_mean), _ptr(ws.int_var), st)
-        _l.check(rc, 'cbfssm_loglik_moments_f64')
-        klp = self.pack_kl if self.pack_kl is not None else self.pack_f
-        rc = lib.cbfssm_elbo_combine_f64(pb, self.cL * self.S, 0.0, _ptr(ws.ll_part), ws.ll_part.numel(), _ptr(ws.kl_part),
-                                         ws.kl_part.numel(), None, 0, _ptr(klp.scal), None, _ptr(ws.out), st)
-        _l.check(rc, 'cbfssm_elbo_combine_f64')
+        lp.cast_f32()
+        _timed(getattr(self, '_prof', None), 'forward_pass', None, lambda: lp.half_forward_pass(lp.prob, st))
+        lp.elbo_tail(self.cL * self.S, 0.0, st, kl_pack=self.pack_kl)
 
     def _constrained(self, p):
         pre = self.pre
@@ -273,7 +249,8 @@ class HipHalfGrad:
         ws = self._workspace(prob)
         with torch.no_grad():
             x0 = self._x0(p, u, y, params).contiguous()
-        self._forward(p, self._constrained(p), x0, u, y, _f64(noise['eps_f'], dev), prob, ws)
+        c = self._constrained(p)
+        self._forward(self._loops(prob, ws, c, u, y, x0, _f64(noise['eps_f'], dev)), p, c)
         self.last_ws = ws
         red2 = None
         if self.dist is not None and not local:
@@ -308,50 +285,18 @@ class HipHalfGrad:
             x0 = x0g.detach().contiguous()
         else:
             x0 = self._x0(p, u, y).contiguous()
-        self._forward(p, c, x0, u, y, eps_f, prob, ws)
+        lp = self._loops(prob, ws, c, u, y, x0, eps_f)
+        self._forward(lp, p, c)
 
         st = _stream()
         pb = C.byref(prob)
-        cL = self.cL
         sf = self.slab_f
         red = ws.red
         lay = C.byref(self.pack_f.layout)
-        N = B * self.S
-        groups = (N + 15) // 16
+        groups = (B * self.S + 15) // 16
         gB = None
-        g_mode = 0
-        if self.f32:
-            # one launch at every tile height; the matrix section of its slab holds G = K^-1 (d loss / d K^-1) K^-1 (full up to
-            # 10 row blocks, the lower block triangle of the symmetrised sum from 13: include/cbfssm_hip.h)
-            g_mode = 2 if self.pack_f.layout.NBLK >= 13 else 1
-            s32 = self.slab32_f
-            rc = self._timed('forward_pass_adjoint', lambda: lib.cbfssm_half_forward_pass_bwd_f32(
-                pb, lay, C.c_void_p(self.pack_f.buf32.data_ptr()), _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y),
-                _ptr(eps_f) if eps_f.numel() else None, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), cL, _ptr(ws.gx0),
-                _ptr(ws.gpart_f), st))
-            _l.check(rc, 'cbfssm_half_forward_pass_bwd_f32')
-            if not self.stash:
-                assert s32 == sf
-                _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), sf, ws.n_f, _ptr(red[:sf]), st), 'reduce f')
-            else:
-                # (the float64 slab of these tile heights has no matrix section: hand it to the tail as the image it expects)
-                nb = self.pack_f.layout.NBLK
-                nimg, og = nb * nb * 256, 2 * nb * 256
-                if getattr(self, '_tmp32', None) is None:
-                    self._tmp32 = torch.zeros(s32 + nimg, dtype=torch.float64, device=dev)
-                t32, gB = self._tmp32[:s32], self._tmp32[s32:]
-                _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), s32, ws.n_f, _ptr(t32), st), 'reduce f')
-                red[:og].copy_(t32[:og])
-                red[og:sf].copy_(t32[og + nimg:])
-                gB.copy_(t32[og:og + nimg])
-        elif not self.stash:
-            rc = self._timed('forward_pass_adjoint', lambda: lib.cbfssm_half_forward_pass_bwd_f64(
-                pb, lay, _ptr(self.pack_f.buf), _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y),
-                _ptr(eps_f) if eps_f.numel() else None, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), cL, _ptr(ws.gx0),
-                _ptr(ws.gpart_f), T - 2, 0, None, None, None, 0, st))
-            _l.check(rc, 'cbfssm_half_forward_pass_bwd_f64')
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), sf, ws.n_f, _ptr(red[:sf]), st), 'reduce f')
-        else:
+        prof = getattr(self, '_prof', None)
+        if self.stash and not self.f32:
             Mp = self.pack_f.layout.Mp
             cols_max = max(groups * 16, self.stash_bytes // (2 * Mp * 8))
             f = dict(dtype=torch.float64, device=dev)
@@ -369,22 +314,32 @@ class HipHalfGrad:
             while True:
                 t_lo = max(0, t_hi - per + 1)
                 cols = groups * max(0, t_hi - t_lo + 1) * 16
-                rc = self._timed('forward_pass_adjoint', lambda: lib.cbfssm_half_forward_pass_bwd_f64(
-                    pb, lay, _ptr(self.pack_f.buf), _ptr(c['var_x']), _ptr(c['var_y']), _ptr(u), _ptr(y),
-                    _ptr(eps_f) if eps_f.numel() else None, _ptr(ws.x), _ptr(ws.fmv_f), _ptr(ws.a2s_f), cL, _ptr(ws.gx0),
-                    _ptr(ws.gpart_f), t_hi, t_lo, _ptr(ws.gx_carry), _ptr(sa), _ptr(sk), cols, st))
-                _l.check(rc, 'cbfssm_half_forward_pass_bwd_f64')
-                _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ws.gpart_f), sf, groups, _ptr(tmp), st), 'reduce f')
+                _timed(prof, 'forward_pass_adjoint', None,
+                       lambda: lp.half_forward_pass_bwd(prob, st, (t_hi, t_lo, sa, sk, cols)))
+                ops.reduce_partials(ws.gpart_f, sf, groups, tmp, st)
                 red[:sf] += tmp
                 if cols:
-                    self._timed('stash_contraction', lambda: self._contract.add(sa, sk, cols, st))
+                    _timed(prof, 'stash_contraction', None, lambda: self._contract.add(sa, sk, cols, st))
                 t_hi = t_lo - 1
                 if t_hi < 0:
                     break
+        else:
+            # one launch for the whole time loop (float32: at every tile height, into the non-stash slab)
+            _timed(prof, 'forward_pass_adjoint', None, lambda: lp.half_forward_pass_bwd(prob, st))
+            if not self.repack32:
+                assert not self.f32 or self.slab32_f == sf
+                ops.reduce_partials(ws.gpart_f, sf, ws.n_f, red[:sf], st)
+            else:
+                s32, nb = self.slab32_f, self.pack_f.layout.NBLK
+                if self._tmp32 is None:
+                    self._tmp32 = torch.zeros(s32 + nb * nb * 256, dtype=torch.float64, device=dev)
+                t32, gB = self._tmp32[:s32], self._tmp32[s32:]
+                ops.reduce_partials(ws.gpart_f, s32, ws.n_f, t32, st)
+                repack_f32(t32, red[:sf], gB, nb)
 
         # data scalars and the log-likelihood's pull on var_y (cbfssmhalf.py:181-189): tail = [loglik, kl_x, 0, d/d var_y]
         tail = red[sf:]
-        _l.check(lib.cbfssm_data_tail_f64(pb, _ptr(c['var_y']), _ptr(ws.ll_part), _ptr(ws.out), cL, _ptr(tail), st),
+        _l.check(lib.cbfssm_data_tail_f64(pb, _ptr(c['var_y']), _ptr(ws.ll_part), _ptr(ws.out), self.cL, _ptr(tail), st),
                  'cbfssm_data_tail_f64')
         gx0_b = ws.gx0.view(B, self.S, self.dim_x).sum(1)        # d loss / d x_0 per sequence (tiled over S, :87)
         rgrads = {}
@@ -394,7 +349,7 @@ class HipHalfGrad:
                                               _ptr(y), _ptr(rflat), _ptr(gru['act']), _ptr(gx0_b.contiguous()), _ptr(gru['gpart']), st)
             _l.check(rc, 'cbfssm_gru_recog_bwd_f64')
             rg = torch.zeros(P, dtype=torch.float64, device=dev)
-            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gru['gpart']), P, B, _ptr(rg), st), 'reduce recog')
+            ops.reduce_partials(gru['gpart'], P, B, rg, st)
             o = 0
             for k in rnames:
                 rgrads[k] = rg[o:o + p[k].numel()].view(p[k].shape)
@@ -430,7 +385,7 @@ class HipHalfGrad:
                 self.tail_work = torch.zeros(nw, dtype=torch.float64, device=dev)
             gall = torch.zeros(ngp + sum(rgrads[k].numel() for k in rnames), dtype=torch.float64, device=dev)
             rc = lib.cbfssm_train_tail_half_f64(lay, _ptr(self.pack_f.buf), _ptr(self.pack_kl.buf) if self.pack_kl is not None else None,
-                                                int(lsc.numel() == 1), _ptr(red), _ptr(gB), 0, g_mode, self.dim_y, _ptr(pflat), _ptr(cflat),
+                                                int(lsc.numel() == 1), _ptr(red), _ptr(gB), 0, g_mode(self.f32, self.pack_f.layout), self.dim_y, _ptr(pflat), _ptr(cflat),
                                                 _ptr(self.tail_work), _ptr(gall), st)
             _l.check(rc, 'cbfssm_train_tail_half_f64')
             grads = FlatDict()
@@ -447,20 +402,10 @@ class HipHalfGrad:
 
         grads = dict(rgrads)
         if self.f32:
-            # (cross-check path) the matrix section holds G = K^-1 (d loss / d K^-1) K^-1; this restatement expects K G K
-            from .train import _unpack_c
-            nb, M = self.pack_f.layout.NBLK, self.M
-            G = _unpack_c(gB if gB is not None else red[2 * nb * 256:2 * nb * 256 + nb * nb * 256], nb, nb)
-            if g_mode == 2:
-                blk = torch.arange(16 * nb, device=dev) // 16
-                G = torch.where(blk[:, None] >= blk[None, :], G, torch.zeros_like(G))
-            G = 0.5 * (G + G.T)[:M, :M]
-            K = self.pack_f.Kmm + self.pack_f.scal[_l.SCAL_JITTER] * torch.eye(M, dtype=torch.float64, device=dev)
-            Bd = torch.zeros(16 * nb, 16 * nb, dtype=torch.float64, device=dev)
-            Bd[:M, :M] = K @ G @ K
-            gB = Bd.view(nb, 4, 4, nb, 16).permute(0, 3, 1, 2, 4).reshape(-1)
-        gz, gmu, gs2, gvar, gls, small = self._gp_adjoint(self.pack_f, red[:sf], p[pre + 'zeta_pos'], c['ls'], c['var'],
-                                                          p[pre + 'zeta_mean'], c['zvar'], self.dim_x, gB, self.pack_kl)
+            gB = kgk_image(self.pack_f, red[:sf], gB)
+        gz, gmu, gs2, gvar, gls, small = _gp_adjoint(self.pack_f, red[:sf], p[pre + 'zeta_pos'], c['ls'], c['var'],
+                                                     p[pre + 'zeta_mean'], c['zvar'], self.dim_x, not self.stash, gB,
+                                                     self.pack_kl)
         grads[pre + 'zeta_pos'] = gz
         grads[pre + 'zeta_mean'] = gmu
         grads[pre + 'zeta_var_unc'] = gs2 * torch.sigmoid(p[pre + 'zeta_var_unc'])
