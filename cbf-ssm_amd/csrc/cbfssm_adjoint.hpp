@@ -11,6 +11,8 @@
 //       mubar += A2 Fm^T,  s2bar += (A2 o A2) Fv^T,  Kinvbar += A2bar K^T      (k-dim = the 16 chains)    MFMA
 //   F   Kbar = Kinv A2bar - A2 o colsum(Fv);  Ebar = Kbar o K                                            MFMA
 //       xbar~ = Z~^T Ebar - x~ o colsum(Ebar),  Zbar~ += Ebar x~^T                                       MFMA
+//       (two 16-row input blocks, D = 9 .. 24: only block 0 -- it holds every state row -- goes through the MFMAs; colsum(Ebar)
+//        is summed in the lanes, the lengthscale adjoint of the rows j >= 16 follows from Zbar~ after the time loop)
 //   G   carry d loss/d x_t (or d loss/d h_t) to the next reverse step, then in the same lanes
 //   D   per-(chain, dim) adjoint of the NEXT step's epilogue -> Fm = d loss/d fmean, Fv = d loss/d fvar  (16 x 16 each)
 //
@@ -69,6 +71,7 @@ struct RevArgs {
                            // (PassArgs::a2s layout); NULL -> phase C recomputes them
     const double* fmv;     // (fmean, fvar) of every step as saved by the forward evaluation (PassArgs::fmv layout)
     int ksave;             // 1: every saved record is [A2 tile][kernel tile] (PassArgs::ksave)
+    int M;                 // inducing points (rows m >= M of the tiles are padding)
 };
 
 // slab layout (doubles), all in MFMA C-layout [r][lane] blocks of 256
@@ -83,6 +86,41 @@ struct Slab {
 };
 
 
+// Input-adjoint geometry.  The D inputs plus the ones row fill JB 16-row blocks.  With two blocks (four or six k-steps of
+// the input dimension: D = 9 .. 24, the state dimension is at most 16) every state row sits in block 0 and the recurrence needs nothing else from the product xbar~ = (Z~)^T Ebar, so only JX = 1
+// block of it is computed per step:
+//   - colsum(Ebar) (the ones row, wherever it sits) is summed in the lanes: 16 doubles per wave in an LDS area of their own;
+//   - the lengthscale adjoint of the rows j >= 16, sum_{t,n} xbar~[j,n] x~[j,n], is
+//         sum_m z~[m,j] Zbar~[m][j]  -  sum_{t,n} colsum(Ebar)[n] x~[j,n]^2
+//     with Zbar~ the accumulator the kernel keeps anyway; the second sum is one fused multiply-add per step and lane.
+// A wave's slot of the partial tiles: JX blocks of 256, and at least the 16 x 17 transpose scratch the eight-wave tiles
+// put there (272 doubles).
+template <int DK>
+struct RevInGeom {
+    static constexpr int JB = (4 * DK + 1 + 15) / 16;
+    static constexpr bool SPLITJ = (JB == 2);
+    static constexpr int JX = SPLITJ ? 1 : JB;
+    static constexpr int PSL = SPLITJ ? 272 : (JB > 2 ? JB : 2) * 256;
+    static constexpr int ECS = SPLITJ ? 16 : 0;                         // column sums of Ebar: doubles per wave
+};
+
+// Sum of a double over the four 16-lane groups of a wave (lanes nl, nl + 16, nl + 32, nl + 48), in every lane.  The gfx950
+// lane swaps exchange the odd 16-lane rows of the first operand with the even rows of the second (permlane16) and the upper
+// half of the first with the lower half of the second (permlane32): with both operands the same value, the two results
+// are the two addends.  Vector ALU only -- an LDS permute would be two round trips here.
+__device__ __forceinline__ double rowgroup_sum(double x)
+{
+    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+    unsigned lo = __double2loint(x), hi = __double2hiint(x);
+    u2 pl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    u2 ph = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    const double y = __hiloint2double(ph[0], pl[0]) + __hiloint2double(ph[1], pl[1]);
+    lo = __double2loint(y); hi = __double2hiint(y);
+    pl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    ph = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double(ph[0], pl[0]) + __hiloint2double(ph[1], pl[1]);
+}
+
 // LDS budget of one adjoint workgroup (doubles).  Stash-mode tiles re-read the Z~ operand images every step instead of
 // holding them in registers; when the K^-1 image does not fit anyway, the LDS left over holds those images (a read
 // that misses L1 costs an L2 round trip right in front of the MFMAs that need it).
@@ -90,17 +128,19 @@ template <int NBLK, int RB, int DK, bool STASH>
 struct RevLds {
     static constexpr int W = (NBLK + RB - 1) / RB;
     static constexpr int JB = (4 * DK + 1 + 15) / 16;
-    static constexpr int PSL = (JB > 2 ? JB : 2) * 256;
-    static constexpr int BASE_PLAIN = 2 * 4 * DK * 17 + 2 * (16 * NBLK) * 17 + 2 * 16 * 17 + W * PSL + 64;
+    static constexpr int JX = RevInGeom<DK>::JX;
+    static constexpr int PSL = RevInGeom<DK>::PSL;
+    static constexpr int ECS = W * RevInGeom<DK>::ECS;
+    static constexpr int BASE_PLAIN = 2 * 4 * DK * 17 + 2 * (16 * NBLK) * 17 + 2 * 16 * 17 + W * PSL + 64 + ECS;
     // Stash-mode tiles that stream K^-1: the per-wave partial tiles of the input adjoint (`part`, written at the end of
     // phase F, read in phase G) live in the K tile's LDS, which is dead by then -- one more workgroup barrier per step
     // buys W x PSL doubles (28 KB at NBLK = 13) for the operand images below.
     static constexpr bool PALIAS = STASH;
     static constexpr int KTR = PALIAS ? ((16 * NBLK) * 17 > W * PSL ? (16 * NBLK) * 17 : W * PSL) : (16 * NBLK) * 17;
-    static constexpr int BASE = PALIAS ? 2 * 4 * DK * 17 + KTR + (16 * NBLK) * 17 + 2 * 16 * 17 + 64 : BASE_PLAIN;
+    static constexpr int BASE = PALIAS ? 2 * 4 * DK * 17 + KTR + (16 * NBLK) * 17 + 2 * 16 * 17 + 64 + ECS : BASE_PLAIN;
     static constexpr int LIMIT = 163840 / 8;
     static constexpr int ZP = NBLK * DK * 64 + 16 * NBLK;          // Z~ A-operand image + row constants
-    static constexpr int ZT = NBLK * JB * 256;                     // (Z~)^T A-operand image
+    static constexpr int ZT = NBLK * JX * 256;                     // (Z~)^T A-operand image (the blocks phase F multiplies)
     static constexpr int MU = NBLK * 256;                          // mu_z B-operand image (phase E)
     // filled in this order (measured at NBLK = 13 / D = 21, where only part fits: {(Z~)^T} and {Z~, mu} are within 1 %)
     static constexpr bool ZTLDS = STASH && (BASE + ZT <= LIMIT);
@@ -187,19 +227,21 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
     double* xq0 = lds;                                  // [2][4*DK][17]: this step's and the next step's inputs
     typedef RevLds<NBLK, RB, DK, STASH> RL;
     constexpr bool PALIAS = RL::PALIAS && !BLDS;        // `part` shares the K tile's LDS (see RevLds)
-    constexpr int PSL = (JB > 2 ? JB : 2) * 256;
+    constexpr bool SPLITJ = RevInGeom<DK>::SPLITJ;      // block 1 of the input adjoint stays off the MFMAs (RevInGeom)
+    constexpr int JX = RevInGeom<DK>::JX, PSL = RevInGeom<DK>::PSL;
     double* Kt = xq0 + 2 * 4 * DK * PD;                 // [MP][17]
     double* A2t = Kt + (PALIAS ? RL::KTR : MP * PD);    // [MP][17]
     double* Fm = A2t + MP * PD;                         // [16][17]
     double* Fv = Fm + 16 * PD;                          // [16][17]
-    double* part = PALIAS ? Kt : (Fv + 16 * PD);        // [W][max(2,JB)][4][64]
+    double* part = PALIAS ? Kt : (Fv + 16 * PD);        // [W][PSL]
     double* red = PALIAS ? (Fv + 16 * PD) : (part + W * PSL);   // 64
     int* xflag = reinterpret_cast<int*>(red);           // extra wave: "A2bar rows of row block rb are written" flags
                                                         // (red itself is only used by the block sums after the time loop)
-    double* Bl = red + 64;                              // BLDS: [NBLK][KSr][64]
+    double* ecs = red + 64;                             // SPLITJ: [W][16] column sums of each wave's rows of Ebar
+    double* Bl = ecs + RL::ECS;                         // BLDS: [NBLK][KSr][64]
     constexpr bool ZLDS = RL::ZLDS && !BLDS, ZTLDS = RL::ZTLDS && !BLDS, MULDS = RL::MULDS && !BLDS;
-    double* ZTl = red + 64;                             // ZTLDS: [NBLK][JB][4][64]
-    double* Zl = ZTl + (ZTLDS ? NBLK * JB * 256 : 0);   // ZLDS: [NBLK][DK][64] then cz [MP]
+    double* ZTl = ecs + RL::ECS;                        // ZTLDS: [NBLK][JX][4][64]
+    double* Zl = ZTl + (ZTLDS ? NBLK * JX * 256 : 0);   // ZLDS: [NBLK][DK][64] then cz [MP]
     double* czl = Zl + NBLK * DK * 64;
     double* mul = Zl + (ZLDS ? RL::ZP : 0);             // MULDS: [NBLK][4][64]
 
@@ -261,7 +303,8 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
         ivy[qi] = (MODE == MODE_FWD) ? 1.0 / vy[qi] : 0.0;
         gcar[qi] = 0.0; gdir[qi] = 0.0; gvx[qi] = 0.0; gvy[qi] = 0.0;
     }
-    // Phase G lanes: input row j = 4*gi + g, gi = w + k*W < NG
+    // Phase G lanes: input row j = 4*gi + g, gi = w + k*W < NG.  SPLITJ: the lanes of the rows j >= 16 accumulate
+    // sum colsum(Ebar)[n] x~[j,n]^2 instead, the term that is subtracted after the time loop
     double glx[GPW];
     double glogsig = 0.0;
 #pragma unroll
@@ -283,7 +326,7 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
         for (int i = tid; i < MP; i += NT) czl[i] = a.pk.cz[i];
     }
     if constexpr (ZTLDS) {
-        for (int i = tid; i < NBLK * JB * 256; i += NT) ZTl[i] = a.rk.ZT[i];
+        for (int i = tid; i < NBLK * JX * 256; i += NT) ZTl[i] = a.rk.ZT[(i / (JX * 256)) * (JB * 256) + i % (JX * 256)];
     }
     if constexpr (MULDS) {
         for (int i = tid; i < NBLK * 256; i += NT) mul[i] = a.rk.muB[i];
@@ -917,11 +960,11 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
         // (Z~)^T operands of the input-adjoint product below: issued here, in flight under the K^-1 A2bar loop (with the
         // eighth wave the row-block waves have the registers for it; the product was 7 % of a step waiting for L2)
         constexpr bool ZTPRE = XW && RB == 1;
-        double ztv[ZTPRE ? JB : 1][4];
+        double ztv[ZTPRE ? JX : 1][4];
         if constexpr (ZTPRE) {
             const double* ZTp0 = a.rk.ZT + rbs[0] * JB * 256 + l;
 #pragma unroll
-            for (int jb = 0; jb < JB; ++jb)
+            for (int jb = 0; jb < JX; ++jb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ztv[jb][r] = ZTp0[(jb * 4 + r) * 64];
         }
@@ -1054,16 +1097,16 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
             }
         }
         CBF_STAMP_MARK(6);
-        d4 xp[JB];
+        d4 xp[JX];
         {
 #pragma unroll
-            for (int jb = 0; jb < JB; ++jb) xp[jb] = d4{0, 0, 0, 0};
+            for (int jb = 0; jb < JX; ++jb) xp[jb] = d4{0, 0, 0, 0};
 #pragma unroll
             for (int i = 0; i < RB; ++i) {
                 if (ok[i]) {
-                    const double* ZTp = (ZTLDS ? ZTl : a.rk.ZT) + rbs[i] * JB * 256 + l;
+                    const double* ZTp = ZTLDS ? (ZTl + rbs[i] * JX * 256 + l) : (a.rk.ZT + rbs[i] * JB * 256 + l);
 #pragma unroll
-                    for (int jb = 0; jb < JB; ++jb)
+                    for (int jb = 0; jb < JX; ++jb)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             xp[jb] = CBF_MFMA(ZTPRE ? ztv[jb][r] : ZTp[(jb * 4 + r) * 64], ebar[i][r], xp[jb]);   // rows j, k = m of this block
@@ -1071,10 +1114,29 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
             }
             if constexpr (!PALIAS && !XW) {
 #pragma unroll
-                for (int jb = 0; jb < JB; ++jb)
+                for (int jb = 0; jb < JX; ++jb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) part[w * PSL + (jb * 4 + r) * 64 + l] = xp[jb][r];
             }
+        }
+        // SPLITJ: column sums of this wave's rows of Ebar (rows m >= M are padding: finite, but not zero) -- what the ones
+        // row of (Z~)^T gives the other geometries.  Behind the MFMAs above in program order: nothing of it waits for them,
+        // and in front of them its two cross-lane steps would sit on the step's chain.
+        if constexpr (SPLITJ) {
+            __builtin_amdgcn_sched_barrier(0);
+            double es[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) {
+                double em[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) em[r] = (ok[i] && 16 * rbs[i] + 4 * r + g < a.M) ? ebar[i][r] : 0.0;
+                es[i] = (em[0] + em[1]) + (em[2] + em[3]);
+            }
+            double ecol = es[0];
+#pragma unroll
+            for (int i = 1; i < RB; ++i) ecol += es[i];
+            ecol = rowgroup_sum(ecol);
+            if (g == 0) ecs[w * 16 + nl] = ecol;        // (last read in phase G of the previous step, two barriers ago)
         }
         CBF_STAMP_MARK(7);
 #pragma unroll
@@ -1105,14 +1167,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
         if constexpr (XW) {
             __builtin_amdgcn_wave_barrier();     // the transposes above went through this slot
 #pragma unroll
-            for (int jb = 0; jb < JB; ++jb)
+            for (int jb = 0; jb < JX; ++jb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) part[w * PSL + (jb * 4 + r) * 64 + l] = xp[jb][r];
         }
         if constexpr (PALIAS) {
             __syncthreads();                 // every wave is done with its rows of the K tile (Ebar, the transposes)
 #pragma unroll
-            for (int jb = 0; jb < JB; ++jb)
+            for (int jb = 0; jb < JX; ++jb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) part[w * PSL + (jb * 4 + r) * 64 + l] = xp[jb][r];
         }
@@ -1121,7 +1183,11 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
 
         // ---- G: input adjoint, carried to the next reverse step
         double esum = 0.0;   // colsum of Ebar for this lane's chain = row D of the xbar tile
-        {
+        if constexpr (SPLITJ) {
+#pragma unroll
+            for (int ww = 0; ww < W; ++ww) esum += ecs[ww * 16 + nl];
+            if (w == 0 && g == 0 && cvalid) glogsig += esum;
+        } else {
             const int jbD = D >> 4, qD = (D >> 2) & 3, gD = D & 3;
 #pragma unroll
             for (int ww = 0; ww < W; ++ww) esum += part[ww * PSL + (jbD * 4 + qD) * 64 + gD * 16 + nl];
@@ -1134,6 +1200,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
             if (gi < NG) {
                 const int jb = gi >> 2, q = gi & 3;
                 const int j = 16 * jb + 4 * q + g;
+                if (SPLITJ && jb > 0) {
+                    // rows off the MFMAs: only the second term of their lengthscale adjoint is accumulated per step
+                    if (j < D && cvalid) {
+                        const double xt = xq[j * PD + nl];
+                        glx[k2] = fma(esum * xt, xt, glx[k2]);
+                    }
+                    continue;
+                }
                 double xb = 0.0;
 #pragma unroll
                 for (int ww = 0; ww < W; ++ww) xb += part[ww * PSL + (jb * 4 + q) * 64 + l];
@@ -1142,7 +1216,7 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
                     xb -= xt * esum;
                     glx[k2] += xb * xt;                                            // lengthscale adjoint (inputs)
                 }
-                if (j == D && cvalid) glogsig += xb;
+                if (!SPLITJ && j == D && cvalid) glogsig += xb;
                 // state rows hand their adjoint to the phase-D lanes of the same (d, chain): identical lanes when
                 // jb == 0 and this wave owns group q in both phases (gi = q for gi < 4)
                 if (jb == 0) {
@@ -1248,6 +1322,23 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
     }
     // small per-dimension sums: reduce over the 16 chains of each 16-lane group, lane nl == 0 writes
     for (int i = tid; i < 192; i += NT) slab[SL::small + i] = 0.0;
+    if constexpr (SPLITJ) {
+        // first term of the lengthscale adjoint of the rows j = 16 + nl: sum_m z~[m,j] Zbar~[m][j].  The (Z~)^T operand image
+        // and the accumulator tile share the lane mapping (row m = 16 rb + 4 r + g, column j = 16 + nl); rows m >= M of the
+        // image are zero.  Per wave in a fixed order, then over the waves in wave order below.  (`part` is free: it was
+        // last read in phase G of the last step, in front of that step's closing barrier.)
+        double zg = 0.0;
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            if (ok[i]) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zg = fma(a.rk.ZT[(rbs[i] * JB + 1) * 256 + r * 64 + l], gZ[i][1][r], zg);
+            }
+        }
+        zg += __shfl_xor(zg, 16);
+        zg += __shfl_xor(zg, 32);
+        if (g == 0) part[w * 16 + nl] = zg;
+    }
     __syncthreads();
 #pragma unroll
     for (int qi = 0; qi < QPW; ++qi) {
@@ -1266,6 +1357,15 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
         double v = glx[k2];
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if constexpr (SPLITJ) {
+            if (gi >= 4 && gi < NG) {
+                const int j = 4 * gi + g;
+                double zs = 0.0;
+                if (j < D)
+                    for (int ww = 0; ww < W; ++ww) zs += part[ww * 16 + (j - 16)];
+                v = zs - v;
+            }
+        }
         if (gi < NG && nl == 0) slab[SL::small + 32 + 4 * gi + g] = v;
     }
     const double s1 = block_sum(gsig, red, tid, NT);

@@ -1274,6 +1274,7 @@ static int fill_rev(RevArgs& a, const cbfssm_problem* p, const cbfssm_pack_layou
     a.recog_len = p->recog_len; a.condition = p->condition; a.k_factor = p->k_factor;
     a.slab = L->rev_slab;
     a.KSr = (L->M + 3) / 4;
+    a.M = L->M;
     if (L->rev_slab <= 0) return fail(-3, "no adjoint kernel for M=%d (tile height %d)", L->M, L->NBLK);
     return 0;
 }
