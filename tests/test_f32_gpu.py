@@ -42,8 +42,15 @@ def test_gp_predict_f32_every_tile_height(M, dim_x, dim_u, dim_y):
 ])
 @pytest.mark.parametrize('cond', [True, False])
 def test_elbo_f32_tracks_f64(kw, cond):
+    _check_elbo_f32_tracks_f64(kw, cond)
+
+
+def _check_elbo_f32_tracks_f64(kw, cond, form=None):
+    """form: 'dense' | 'tri' pins the GP form of both engines (config['gp_form'])"""
     w = syn.tiny(loss_factors=(2., 0.7), **kw)
     cfg = w.model_config()
+    if form:
+        cfg['gp_form'] = form
     p = syn.perturb_params(syn.make_params(w, seed=1), scale=0.1)
     u, y = syn.make_inputs(w, seed=0)
     noise = syn.make_noise(w, seed=2)
@@ -54,6 +61,10 @@ def test_elbo_f32_tracks_f64(kw, cond):
     o32 = e32.run(u, y, noise, condition=cond)
     a, b = o64.out.cpu().numpy(), o32.out.cpu().numpy()
     assert b[7] == 0.0
+    assert form is None or e32.gp_form() == form + '/' + form
+    print('float32 forward M=%d D=%d condition=%d form=%s: loss rel %.1e, x %.1e of max' % (
+        w.M, w.D, cond, form, abs(b[6] - a[6]) / abs(a[6]),
+        float((o32.x - o64.x).abs().max() / o64.x.abs().max())))
     for i, name in enumerate(('loglik', 'kl_x', 'entropy')):
         assert b[i] == pytest.approx(a[i], rel=2e-4, abs=1e-3), name
     assert b[3] == a[3] and b[4] == a[4]                    # the prior KL comes from the float64 prepare

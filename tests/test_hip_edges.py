@@ -11,11 +11,14 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
 
-def _run(kw, condition=True, grads=True, scale=0.1):
+def _run(kw, condition=True, grads=True, scale=0.1, form=None):
+    """form: 'dense' | 'tri' pins the GP form (config['gp_form']) and asserts that both packs run it."""
     from oracle import cbfssm_oracle as orc
     from oracle import cbfssm_torch_ref as tref
     w = syn.tiny(**kw)
     cfg = w.model_config()
+    if form:
+        cfg['gp_form'] = form
     p = syn.perturb_params(syn.make_params(w, seed=1), scale=scale)
     u, y = syn.make_inputs(w)
     noise = syn.make_noise(w)
@@ -24,6 +27,13 @@ def _run(kw, condition=True, grads=True, scale=0.1):
     params = {k: torch.tensor(v, device=DEV) for k, v in p.items()}
     loss, terms, ws = eng.forward(params, u, y, noise, condition)
     assert float(terms['info']) == 0.0
+    if form:
+        assert eng.pack_f.gp_form() == form and eng.pack_b.gp_form() == form
+    print('M=%d D=%d condition=%d form=%s: loss rel %.1e, x %.1e, pred_mean %.1e, pred_var rel %.1e' % (
+        w.M, w.D, condition, form, abs(float(loss) - ref['loss']) / abs(ref['loss']),
+        np.abs(ops.as_btsd(ws.x, w.B, w.S).cpu().numpy() - ref['x_final']).max(),
+        np.abs(ws.pred_mean.cpu().numpy() - ref['pred_mean']).max(),
+        (np.abs(ws.pred_var.cpu().numpy() - ref['pred_var']) / ref['pred_var']).max()))
     assert float(loss) == pytest.approx(ref['loss'], rel=1e-9)
     np.testing.assert_allclose(ops.as_btsd(ws.x, w.B, w.S).cpu().numpy(), ref['x_final'], rtol=1e-8, atol=1e-10)
     np.testing.assert_allclose(ws.pred_mean.cpu().numpy(), ref['pred_mean'], rtol=1e-8, atol=1e-10)

@@ -57,15 +57,21 @@ def test_kmm_chol_reports_non_pd():
 @pytest.mark.parametrize('M,dim_x,dim_u,dim_y', [(12, 5, 2, 2), (20, 4, 1, 1), (50, 4, 1, 1), (100, 14, 7, 7),
                                                 (130, 9, 3, 2), (200, 14, 7, 7), (250, 4, 2, 2), (300, 4, 2, 2)])
 def test_gp_prepare_and_predict(M, dim_x, dim_u, dim_y):
-    orc = _oracle()
     w = syn.tiny(M=M, dim_x=dim_x, dim_u=dim_u, dim_y=dim_y)
-    p = syn.perturb_params(syn.make_params(w, seed=M))
+    _check_prepare_and_predict(w, syn.perturb_params(syn.make_params(w, seed=M)))
+
+
+def _check_prepare_and_predict(w, p, form=None):
+    """forward and backward GP of workload w at parameters p against oracle.GPModel; form: 'dense' | 'tri' pins the GP form"""
+    orc = _oracle()
+    M, dim_x, dim_y = w.M, w.dim_x, w.dim_y
     rng = np.random.default_rng(7)
     for g, Do in (('f', dim_x), ('b', dim_x - dim_y)):
         args = _gp_args(p, g)
         gp = orc.GPModel(p[g + '.zeta_pos'], p[g + '.zeta_mean'], p[g + '.zeta_var_unc'], p[g + '.variance_unc'],
                          p[g + '.lengthscales_unc'])
-        pack = ops.GPPack(M, w.D, Do, DEV).prepare(*[torch.tensor(a, device=DEV) for a in args])
+        pack = ops.GPPack(M, w.D, Do, DEV, form).prepare(*[torch.tensor(a, device=DEV) for a in args])
+        assert form is None or pack.gp_form() == form
         scal = pack.scal.cpu().numpy()
         assert scal[lib.SCAL_INFO] == 0.0
         K = gp.kern.K(gp.zeta_pos) + 1e-8 * np.eye(M)
@@ -76,6 +82,8 @@ def test_gp_prepare_and_predict(M, dim_x, dim_u, dim_y):
             X = rng.standard_normal((npts, w.D)) * 1.5
             fm, fv = pack.predict(torch.tensor(X, device=DEV))
             fm_ref, fv_ref = gp.predict(X)
+            print('predict M=%d D=%d Do=%d form=%s npts=%d: fmean %.1e fvar %.1e' % (
+                M, w.D, Do, form, npts, np.abs(fm.cpu().numpy() - fm_ref).max(), np.abs(fv.cpu().numpy() - fv_ref).max()))
             np.testing.assert_allclose(fm.cpu().numpy(), fm_ref, rtol=1e-8, atol=1e-11)
             np.testing.assert_allclose(fv.cpu().numpy(), fv_ref, rtol=1e-8, atol=1e-11)
 
