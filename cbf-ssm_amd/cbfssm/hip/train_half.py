@@ -4,8 +4,10 @@ entropy term (cbfssmhalf.py:174-199).
 
 The time loop and its adjoint run in the same kernels as CBFSSM's forward pass (problem.half = 1,
 include/cbfssm_hip.h: cbfssm_half_forward_pass_f64 / _bwd_f64).  The recognition model is a GRU(16) over
-recog_len steps + a dense layer on B sequences (cbfssmhalf.py:82-93) -- a few hundred FLOPs per sequence; it stays in
-PyTorch autograd (float64, TF-1.8 GRUCell gate layout) and receives d loss / d x_0 from the adjoint kernel.
+recog_len steps + a dense layer on B sequences (cbfssmhalf.py:82-93), or for PR-SSM conv1d -> max_pool -> dense in float32
+(prssm.py:146-157) -- a few hundred FLOPs per sequence: two launches each (cbfssm_gru_recog[_bwd]_f64,
+cbfssm_conv_recog[_bwd]_f32), the backward one taking d loss / d x_0 from the adjoint kernel.  The tensor-library
+restatements below stay as cross-checks (CBFSSM_TORCH_GRU=1, CBFSSM_TORCH_CONV=1) and for shapes beyond the kernels' limits.
 """
 import ctypes as C
 import os
@@ -116,6 +118,12 @@ class HipHalfGrad:
         # library launches through autograd; CBFSSM_TORCH_GRU=1 keeps the latter (same numbers, a cross-check)
         self.fused_gru = self.rnn and not os.environ.get('CBFSSM_TORCH_GRU')
         self._gru = {}
+        # the conv recognition model likewise (cbfssm_conv_recog[_bwd]_f32); CBFSSM_TORCH_CONV=1 keeps conv_recognition below,
+        # which also serves a recog_len beyond the kernels' limits (the library says where they are: param_elems < 0)
+        self.fused_conv = (self.conv and not os.environ.get('CBFSSM_TORCH_CONV') and
+                           int(_l.load().cbfssm_conv_recog_param_elems(self.dim_u, self.dim_y, self.dim_x,
+                                                                       int(config['recog_len']))) >= 0)
+        self._conv = {}
 
     def _problem(self, B, T, condition):
         c = self.config
@@ -135,12 +143,14 @@ class HipHalfGrad:
         return conv_recognition(rp, u, y, self.config['recog_len'])
 
     def _recog_flat(self, params, p):
-        """the six recognition tensors as one flat vector: the tail of the optimiser's own storage when `params` are its views"""
+        """the recognition tensors (six of the GRU, four of the conv model) as one flat vector: the tail of the optimiser's own
+        storage when `params` are its views"""
+        names = self._recog_params(p)
         flat = getattr(params, 'flat', None)
-        n = sum(p[k].numel() for k in RECOG_NAMES)
-        if flat is not None and flat.device == self.device and tuple(params.keys())[-6:] == RECOG_NAMES:
+        n = sum(p[k].numel() for k in names)
+        if flat is not None and flat.device == self.device and tuple(params.keys())[-len(names):] == names:
             return flat[flat.numel() - n:]
-        return torch.cat([p[k].reshape(-1) for k in RECOG_NAMES])
+        return torch.cat([p[k].reshape(-1) for k in names])
 
     def _gru_forward(self, rflat, u, y, keep):
         lib = _l.load()
@@ -159,9 +169,27 @@ class HipHalfGrad:
         _l.check(rc, 'cbfssm_gru_recog_f64')
         return g
 
+    def _conv_forward(self, rflat, u, y):
+        lib = _l.load()
+        B, T = u.shape[0], u.shape[1]
+        R = min(int(self.config['recog_len']), T)
+        key = (B, R)
+        if key not in self._conv:
+            f = dict(dtype=torch.float64, device=self.device)
+            P = int(lib.cbfssm_conv_recog_param_elems(self.dim_u, self.dim_y, self.dim_x, R))
+            self._conv[key] = {'x0': torch.zeros(B, self.dim_x, **f), 'P': P, 'R': R,
+                               'gpart': torch.zeros((B + 32) * max(P, 0), **f)}
+        g = self._conv[key]
+        rc = lib.cbfssm_conv_recog_f32(B, T, self.dim_u, self.dim_y, self.dim_x, R, _ptr(u), _ptr(y), _ptr(rflat), _ptr(g['x0']),
+                                       _stream())
+        _l.check(rc, 'cbfssm_conv_recog_f32')
+        return g
+
     def _x0(self, p, u, y, params=None):
         if self.fused_gru:
             return self._gru_forward(self._recog_flat(params, p), u, y, keep=False)['x0']
+        if self.fused_conv:
+            return self._conv_forward(self._recog_flat(params, p), u, y)['x0']
         if self.rnn or self.conv:
             return self._recog(p, u, y)
         B = u.shape[0]
@@ -274,11 +302,15 @@ class HipHalfGrad:
         eps_f = _f64(noise['eps_f'], dev)
         rp = {}
         rnames = self._recog_params(p)
-        gru = None
+        gru = conv = None
         if self.fused_gru:
             rflat = self._recog_flat(params, p)
             gru = self._gru_forward(rflat, u, y, keep=True)
             x0 = gru['x0']
+        elif self.fused_conv:
+            rflat = self._recog_flat(params, p)
+            conv = self._conv_forward(rflat, u, y)
+            x0 = conv['x0']
         elif rnames:
             rp = {k: p[k].detach().clone().requires_grad_(True) for k in rnames}
             x0g = self._recog(rp, u, y)
@@ -343,13 +375,19 @@ class HipHalfGrad:
                  'cbfssm_data_tail_f64')
         gx0_b = ws.gx0.view(B, self.S, self.dim_x).sum(1)        # d loss / d x_0 per sequence (tiled over S, :87)
         rgrads = {}
-        if gru is not None:
-            P = gru['P']
-            rc = lib.cbfssm_gru_recog_bwd_f64(B, T, self.dim_u, self.dim_y, self.dim_x, min(int(self.config['recog_len']), T), _ptr(u),
-                                              _ptr(y), _ptr(rflat), _ptr(gru['act']), _ptr(gx0_b.contiguous()), _ptr(gru['gpart']), st)
-            _l.check(rc, 'cbfssm_gru_recog_bwd_f64')
+        if gru is not None or conv is not None:
+            if gru is not None:
+                P, gpart = gru['P'], gru['gpart']
+                rc = lib.cbfssm_gru_recog_bwd_f64(B, T, self.dim_u, self.dim_y, self.dim_x, min(int(self.config['recog_len']), T), _ptr(u),
+                                                  _ptr(y), _ptr(rflat), _ptr(gru['act']), _ptr(gx0_b.contiguous()), _ptr(gpart), st)
+                _l.check(rc, 'cbfssm_gru_recog_bwd_f64')
+            else:
+                P, gpart = conv['P'], conv['gpart']
+                rc = lib.cbfssm_conv_recog_bwd_f32(B, T, self.dim_u, self.dim_y, self.dim_x, conv['R'], _ptr(u), _ptr(y), _ptr(rflat),
+                                                   _ptr(gx0_b.contiguous()), _ptr(gpart), st)
+                _l.check(rc, 'cbfssm_conv_recog_bwd_f32')
             rg = torch.zeros(P, dtype=torch.float64, device=dev)
-            ops.reduce_partials(gru['gpart'], P, B, rg, st)
+            ops.reduce_partials(gpart, P, B, rg, st)
             o = 0
             for k in rnames:
                 rgrads[k] = rg[o:o + p[k].numel()].view(p[k].shape)
@@ -421,10 +459,10 @@ class HipHalfGrad:
 
 class HipHalfTrainStep:
     """One `sess.run((model.train, model.loss))` of a forward-only variant (training/trainer.py:40) as ONE HIP-graph replay:
-    the recognition model forward and its autograd backward (GRU(16) over recog_len steps: a few hundred tiny launches, most
-    of an eager step at the small-scale shapes), K_mm / Cholesky / K^-1, the pass, its adjoint, the train tail and the Adam
-    update.  One graph per (shapes, condition, GP form), captured at first use; single device (a data-parallel run keeps
-    eager launches around its collective)."""
+    the recognition model forward and backward (two launches; through the tensor library's autograd under CBFSSM_TORCH_GRU /
+    CBFSSM_TORCH_CONV: a few hundred tiny launches for the GRU, most of an eager step at the small-scale shapes), K_mm /
+    Cholesky / K^-1, the pass, its adjoint, the train tail and the Adam update.  One graph per (shapes, condition, GP form),
+    captured at first use; single device (a data-parallel run keeps eager launches around its collective)."""
 
     def __init__(self, engine, opt, graph=None):
         self.engine, self.opt = engine, opt

@@ -182,7 +182,7 @@ class CBFSSM(BaseModel):
 
     def _train_stepper(self):
         """The HIP-graph stepper over this model's engine and optimiser: HipTrainStep for CBFSSM, HipHalfTrainStep for the
-        forward-only variants (their recognition network's autograd launches are captured too)."""
+        forward-only variants (their recognition network's launches are captured too)."""
         from ..hip.train import HipElboGrad, HipTrainStep
         from ..hip.train_half import HipHalfGrad, HipHalfTrainStep
         if getattr(self, '_stepper', None) is None or self._stepper.engine is not self._engine:

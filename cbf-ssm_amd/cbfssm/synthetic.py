@@ -139,7 +139,8 @@ def make_params(w: Workload, seed=1):
 def make_variant_params(w: Workload, variant='half', recog='rnn', seed=1):
     """(config, initial parameters) of the forward-only variants at run-script initial values: CBFSSMHALF
     (cbfssm/model/cbfssmhalf.py:20-47,82-93: gp_f only, var_y with dim_y entries, GRU(16) recognition model with TF's
-    glorot-uniform / GRUCell initial values) or PRSSM (cbfssm/model/prssm.py:28-47: one shared lengthscale)."""
+    glorot-uniform / GRUCell initial values) or PRSSM (cbfssm/model/prssm.py:28-47: one shared lengthscale; recog 'conv': its
+    conv1d -> max_pool -> dense recognition model)."""
     cfg = w.model_config()
     cfg['var_y'] = np.asarray([w.var_y] * w.dim_y)
     cfg['recog_model'] = recog
@@ -161,6 +162,11 @@ def make_variant_params(w: Workload, variant='half', recog='rnn', seed=1):
         p.update({'recog.gate_kernel': glorot(n_in + H, 2 * H), 'recog.gate_bias': np.ones(2 * H),
                   'recog.cand_kernel': glorot(n_in + H, H), 'recog.cand_bias': np.zeros(H),
                   'recog.dense_kernel': glorot(H, w.dim_x), 'recog.dense_bias': np.zeros(w.dim_x)})
+    elif recog == 'conv':                # prssm.py:146-157: tf.layers defaults (glorot-uniform kernels, zero biases)
+        n_in, flat = w.dim_u + w.dim_y, 5 * ((w.recog_len - 2) // 2)
+        lim = np.sqrt(6.0 / (3 * n_in + 3 * 5))
+        p.update({'recog.conv_kernel': rng.uniform(-lim, lim, size=(3, n_in, 5)), 'recog.conv_bias': np.zeros(5),
+                  'recog.dense_kernel': glorot(flat, w.dim_x), 'recog.dense_bias': np.zeros(w.dim_x)})
     return cfg, {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in p.items()}
 
 

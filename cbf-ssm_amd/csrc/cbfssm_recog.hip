@@ -7,6 +7,8 @@
 // of a 4.1 ms step at the Actuator shape even inside a HIP graph).  Here: ONE wave per sequence walks the recog_len steps,
 // forwards (keeping h, r, u, c of every step: 64 doubles) and backwards; the weight gradients leave as one slab per
 // sequence and are summed in a fixed order by cbfssm_reduce_partials_f64 (no atomics: reproducible).
+//
+// Behind the GRU: PR-SSM's other recogniser, conv1d -> max_pool -> dense in float32 (prssm.py:146-157), in the same shape.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -195,6 +197,161 @@ static int fill_gru(GruArgs& a, int B, int T, int dim_u, int dim_y, int dim_x, i
     return 0;
 }
 
+// ---- PR-SSM's conv recognition model (cbfssm/model/prssm.py:146-157) ---------------------------------------------------
+// x_0 = dense(flatten(max_pool(2, 2)(relu(conv1d(5 filters, width 3, valid)(float32(first recog_len steps of [u, y]))))))
+// in float32 arithmetic, as the reference casts it.  ONE wave per sequence: the window and the four tensors are staged
+// in LDS (rounded to float32 as they are read); lane j = 5 p + f owns pooled output (p, f) -- its two pre-activations, the
+// relu and the max stay in registers, so pooling needs no exchange; lanes d < dim_x then do the dense layer.  The
+// backward kernel keeps no activations: it recomputes the forward in the same device function (same operation order =>
+// the same pooling winners and relu mask, bit for bit) and then its lanes own entries of the sequence's gradient slab.
+constexpr int CONV_F = 5, CONV_W = 3;     // prssm.py:150
+constexpr int CONV_MAXR = 64;             // recog_len: an 8 KB window at 32 inputs
+constexpr int CONV_MAXP = (CONV_MAXR - 2) / 2;
+
+struct ConvArgs {
+    int B, T, dim_u, dim_y, dim_x, R, P;
+    const double* u;
+    const double* y;
+    const double* K;      // [3][n_in][5]   (TensorFlow's layout)
+    const double* bc;     // [5]
+    const double* Wd;     // [5 P][dim_x]   rows in (time, channel) order
+    const double* bd;     // [dim_x]
+    double* x0;           // [B][dim_x]
+    const double* gx0;    // [B][dim_x]   d loss / d x_0
+    double* gpart;        // [B][E]       per-sequence gradient slabs, the four tensors behind each other
+    int64_t E;
+};
+
+struct ConvShared {
+    float x[CONV_MAXR * GRU_MAXIN];       // the window, [t][i]
+    float K[CONV_W * GRU_MAXIN * CONV_F];
+    float Wd[CONV_F * CONV_MAXP * GRU_H];
+    float pool[CONV_F * CONV_MAXP];
+    float gpre[(CONV_MAXR - 2) * CONV_F]; // d loss / d pre-activation, [t][f]
+    float bc[CONV_F], bd[GRU_H], gx[GRU_H];
+    int win[CONV_F * CONV_MAXP];          // position of the pooling winner when its pre-activation is positive, else -1
+};
+
+__device__ __forceinline__ float conv_pre(const ConvShared& s, int n_in, int t, int f)
+{
+    float acc = s.bc[f];
+    const float* xr = s.x + t * n_in;                                        // rows t .. t + 2 are contiguous: [w][i]
+    for (int k = 0; k < CONV_W * n_in; ++k) acc = fmaf(xr[k], s.K[k * CONV_F + f], acc);
+    return acc;
+}
+
+// stages the operands and leaves pool / win in LDS (synchronised); returns x_0[b][l] on lanes l < dim_x
+__device__ __forceinline__ float conv_forward(const ConvArgs& a, ConvShared& s, int b, int l)
+{
+    const int n_in = a.dim_u + a.dim_y, npool = CONV_F * a.P;
+    for (int e = l; e < a.R * n_in; e += 64) {
+        const int t = e / n_in, i = e - t * n_in;
+        s.x[e] = float((i < a.dim_u) ? a.u[(int64_t(b) * a.T + t) * a.dim_u + i]
+                                     : a.y[(int64_t(b) * a.T + t) * a.dim_y + (i - a.dim_u)]);
+    }
+    for (int e = l; e < CONV_W * n_in * CONV_F; e += 64) s.K[e] = float(a.K[e]);
+    for (int e = l; e < npool * a.dim_x; e += 64) s.Wd[e] = float(a.Wd[e]);
+    if (l < CONV_F) s.bc[l] = float(a.bc[l]);
+    if (l < a.dim_x) s.bd[l] = float(a.bd[l]);
+    __syncthreads();
+    for (int j = l; j < npool; j += 64) {
+        const int p = j / CONV_F, f = j - p * CONV_F;
+        const float p0 = conv_pre(s, n_in, 2 * p, f), p1 = conv_pre(s, n_in, 2 * p + 1, f);
+        const float a0 = fmaxf(p0, 0.0f), a1 = fmaxf(p1, 0.0f);
+        const bool first = a0 >= a1;                                         // a tie goes to the first element
+        s.pool[j] = first ? a0 : a1;
+        s.win[j] = ((first ? p0 : p1) > 0.0f) ? 2 * p + (first ? 0 : 1) : -1;   // relu'(0) = 0
+    }
+    __syncthreads();
+    float acc = 0.0f;
+    if (l < a.dim_x) {
+        acc = s.bd[l];
+        for (int j = 0; j < npool; ++j) acc = fmaf(s.pool[j], s.Wd[j * a.dim_x + l], acc);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(64) void conv_forward_kernel(ConvArgs a)
+{
+    __shared__ ConvShared s;
+    const int l = threadIdx.x, b = blockIdx.x;
+    const float v = conv_forward(a, s, b, l);
+    if (l < a.dim_x) a.x0[int64_t(b) * a.dim_x + l] = double(v);
+}
+
+__global__ __launch_bounds__(64) void conv_backward_kernel(ConvArgs a)
+{
+    __shared__ ConvShared s;
+    const int l = threadIdx.x, b = blockIdx.x;
+    const int n_in = a.dim_u + a.dim_y, npool = CONV_F * a.P, npre = a.R - 2, dx = a.dim_x;
+    double* gK = a.gpart + int64_t(b) * a.E;
+    double* gbc = gK + CONV_W * n_in * CONV_F;
+    double* gWd = gbc + CONV_F;
+    double* gbd = gWd + npool * dx;
+    conv_forward(a, s, b, l);
+    if (l < dx) s.gx[l] = float(a.gx0[int64_t(b) * dx + l]);
+    for (int e = l; e < npre * CONV_F; e += 64) s.gpre[e] = 0.0f;
+    __syncthreads();
+    // dense layer: x_0 = pool W_d + b_d
+    for (int e = l; e < npool * dx; e += 64) {
+        const int j = e / dx;
+        gWd[e] = double(s.pool[j] * s.gx[e - j * dx]);
+    }
+    if (l < dx) gbd[l] = double(s.gx[l]);
+    // through the pooling and the relu: the winner of each pair takes the pooled output's adjoint if it is positive
+    for (int j = l; j < npool; j += 64) {
+        float g = 0.0f;
+        for (int d = 0; d < dx; ++d) g = fmaf(s.Wd[j * dx + d], s.gx[d], g);
+        if (s.win[j] >= 0) s.gpre[s.win[j] * CONV_F + (j % CONV_F)] = g;
+    }
+    __syncthreads();
+    // conv kernel entry (w, i, f) and the conv bias: one lane sums over the positions in ascending order
+    for (int e = l; e < CONV_W * n_in * CONV_F; e += 64) {
+        const int k = e / CONV_F, f = e - k * CONV_F;                        // k = w n_in + i: x[t + w][i] = x[t n_in + k]
+        float g = 0.0f;
+        for (int t = 0; t < npre; ++t) g = fmaf(s.x[t * n_in + k], s.gpre[t * CONV_F + f], g);
+        gK[e] = double(g);
+    }
+    if (l < CONV_F) {
+        float g = 0.0f;
+        for (int t = 0; t < npre; ++t) g += s.gpre[t * CONV_F + l];
+        gbc[l] = double(g);
+    }
+}
+
+static int64_t conv_elems(int dim_u, int dim_y, int dim_x, int recog_len)
+{
+    const int64_t n_in = int64_t(dim_u) + dim_y, P = (recog_len - 2) / 2;
+    return CONV_W * n_in * CONV_F + CONV_F + CONV_F * P * dim_x + dim_x;
+}
+
+// -1: not a conv recognition model at all; -3: one the kernels have no room for; 0: fine
+static int conv_dims(int dim_u, int dim_y, int dim_x, int recog_len)
+{
+    if (dim_u < 0 || dim_y < 1 || dim_x < 1 || recog_len < 4) return -1;
+    if (int64_t(dim_u) + dim_y > GRU_MAXIN || dim_x > GRU_H || recog_len > CONV_MAXR) return -3;
+    return 0;
+}
+
+static int fill_conv(ConvArgs& a, int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                     const double* params)
+{
+    if (B < 1 || T < 1) return fail(-1, "bad dimensions");
+    const int rc = conv_dims(dim_u, dim_y, dim_x, recog_len);
+    if (rc == -1) return fail(-1, "bad dimensions (conv recognition: dim_y >= 1, dim_x >= 1, recog_len >= 4)");
+    if (rc) return fail(-3, "conv recognition kernel limits: dim_u + dim_y <= 32, dim_x <= 16, recog_len <= 64");
+    if (recog_len > T) return fail(-1, "recog_len exceeds the sequence length");
+    if (!u && dim_u > 0) return fail(-1, "null pointer");
+    if (!y || !params) return fail(-1, "null pointer");
+    const int n_in = dim_u + dim_y;
+    a.B = B; a.T = T; a.dim_u = dim_u; a.dim_y = dim_y; a.dim_x = dim_x; a.R = recog_len; a.P = (recog_len - 2) / 2;
+    a.u = u; a.y = y;
+    a.K = params; a.bc = a.K + CONV_W * n_in * CONV_F; a.Wd = a.bc + CONV_F; a.bd = a.Wd + CONV_F * a.P * dim_x;
+    a.E = conv_elems(dim_u, dim_y, dim_x, recog_len);
+    a.x0 = nullptr; a.gx0 = nullptr; a.gpart = nullptr;
+    return 0;
+}
+
 }  // namespace cbfssm
 
 using namespace cbfssm;
@@ -237,6 +394,38 @@ int cbfssm_gru_recog_bwd_f64(int B, int T, int dim_u, int dim_y, int dim_x, int 
     hipLaunchKernelGGL(gru_backward_kernel, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail(-int(e) - 1000, "gru backward launch failed");
+}
+
+int64_t cbfssm_conv_recog_param_elems(int dim_u, int dim_y, int dim_x, int recog_len)
+{
+    const int rc = conv_dims(dim_u, dim_y, dim_x, recog_len);
+    return rc ? rc : conv_elems(dim_u, dim_y, dim_x, recog_len);
+}
+
+int cbfssm_conv_recog_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                          const double* params, double* x0, void* stream)
+{
+    ConvArgs a;
+    int rc = fill_conv(a, B, T, dim_u, dim_y, dim_x, recog_len, u, y, params);
+    if (rc) return rc;
+    if (!x0) return fail(-1, "null pointer");
+    a.x0 = x0;
+    hipLaunchKernelGGL(conv_forward_kernel, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(-int(e) - 1000, "conv recognition forward launch failed");
+}
+
+int cbfssm_conv_recog_bwd_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                              const double* params, const double* gx0, double* gpart, void* stream)
+{
+    ConvArgs a;
+    int rc = fill_conv(a, B, T, dim_u, dim_y, dim_x, recog_len, u, y, params);
+    if (rc) return rc;
+    if (!gx0 || !gpart) return fail(-1, "null pointer");
+    a.gx0 = gx0; a.gpart = gpart;
+    hipLaunchKernelGGL(conv_backward_kernel, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(-int(e) - 1000, "conv recognition backward launch failed");
 }
 
 }  // extern "C"

@@ -456,6 +456,27 @@ int cbfssm_gru_recog_f64(int B, int T, int dim_u, int dim_y, int dim_x, int reco
 int cbfssm_gru_recog_bwd_f64(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
                              const double* params, const double* act, const double* gx0, double* gpart, void* stream);
 
+/*
+ * PR-SSM's conv recognition model (cbfssm/model/prssm.py:146-157): x_0 = dense(flatten(max_pooling1d(2, 2)(conv1d(5
+ * filters, width 3, relu)(float32(the first recog_len steps of [u, y]))))), cast back to float64.  `_f32`: the arithmetic is
+ * float32 as the reference casts it; every buffer is float64 like the other buffers of this interface, each value
+ * rounded to float32 as it is read.  With n_in = dim_u + dim_y, P = (recog_len - 2) / 2 (an odd last conv position is
+ * dropped by the pooling), params: the four tensors behind each other -- conv kernel [3][n_in][5] (TensorFlow's layout),
+ * conv bias [5], dense kernel [5 P][dim_x] (rows in (time, channel) order), dense bias [dim_x] =
+ * cbfssm_conv_recog_param_elems doubles (host arithmetic; -1 for bad dimensions, -3 beyond the limits below).
+ * One wave per sequence; nothing is kept for the gradient: the backward call recomputes the forward in the same
+ * operation order (the same pooling winners and relu mask), takes d loss / d x_0 per sequence (the adjoint pass's gx0
+ * summed over the particles) and writes one gradient slab of cbfssm_conv_recog_param_elems doubles per sequence (gpart:
+ * room for B + CBFSSM_REDUCE_SPLIT slabs); cbfssm_reduce_partials_f64(gpart, elems, B, out) sums them in a fixed order.
+ * Sub-gradients: relu'(0) = 0, a pooling tie goes to the first element.
+ * Limits: 4 <= recog_len <= T, dim_y >= 1 (else -1); dim_u + dim_y <= 32, dim_x <= 16, recog_len <= 64 (else -3).
+ */
+int64_t cbfssm_conv_recog_param_elems(int dim_u, int dim_y, int dim_x, int recog_len);
+int cbfssm_conv_recog_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                          const double* params, double* x0, void* stream);
+int cbfssm_conv_recog_bwd_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                              const double* params, const double* gx0, double* gpart, void* stream);
+
 /* The rank-local data terms of the flat reduce buffer: tail[0..2] = loglik, kl_x, entropy (from the ELBO combination's
  * out[0..2]); tail[3 + d] = d loss / d var_y[d] through the log-likelihood (cbfssm.py:245-251), d < dim_y, from the
  * per-dimension totals of ll_part (cbfssm_loglik_moments_f64).  cL = loss_factors[0] / S. */
