@@ -358,6 +358,8 @@ class TimeLoops:
         self.var_x, self.var_y, self.u, self.y, self.x0, self.eps_f, self.hid_b, self.eps_b = \
             var_x, var_y, u, y, x0, eps_f, hid_b, eps_b
         self.cL, self.cE, self.f32, self.bf16 = cL, cE, f32, bf16
+        # input gradients: (gin_f, gin_b, gyo) per-chain buffers -> the adjoints run their `_in` entry points (float64)
+        self.in_bufs = None
 
     def cast_f32(self):
         """float32: the packs' float32 images of this evaluation's prepare (one launch per pack, backward GP first)"""
@@ -396,7 +398,12 @@ class TimeLoops:
         """chunk = (t_hi, t_lo, stash_a, stash_k, cols): one stash-mode launch over steps t_hi .. t_lo (float64, M > 112)"""
         lib, ws = _l.load(), self.ws
         a = self._fwd_args(q, ws.y2) + (self.cL, _ptr(ws.gy2), _ptr(ws.gpart_f))
-        if chunk is None:
+        if self.in_bufs is not None:
+            t_hi, t_lo, sa, sk, cols = chunk or (q.T - 2, 0, None, None, 0)
+            _l.check(lib.cbfssm_forward_pass_bwd_in_f64(*a, t_hi, t_lo, _ptr(ws.gx_carry) if chunk else None, _ptr(sa), _ptr(sk),
+                                                        cols, _ptr(self.in_bufs[0]), _ptr(self.in_bufs[2]), st),
+                     'cbfssm_forward_pass_bwd_in_f64')
+        elif chunk is None:
             self._check(lib.cbfssm_forward_pass_bwd_f32(*a, st) if self.f32 else lib.cbfssm_forward_pass_bwd_f64(*a, st),
                         'forward_pass_bwd')
         else:
@@ -408,13 +415,31 @@ class TimeLoops:
         """chunk = (seg0, seg1, stash_a, stash_k, cols): one stash-mode launch over the segments [seg0, seg1) of both runs"""
         lib, ws = _l.load(), self.ws
         a = self._bwd_args(q) + (_ptr(ws.h_all), _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.gy2), self.cE, _ptr(ws.gpart_b))
-        if chunk is None:
+        if self.in_bufs is not None:
+            if chunk is None:       # the whole sweep, chunked over grid.z as cbfssm_backward_pass_bwd_f64 does
+                groups = (q.B * q.S + 15) // 16
+                nchunk = int(lib.cbfssm_rev_workgroups(C.byref(q), 1)) // (2 * groups)
+                chunk = (0, int(lib.cbfssm_bwd_segments(C.byref(q))), None, None, 0)
+            else:
+                nchunk = 1
+            seg0, seg1, sa, sk, cols = chunk
+            _l.check(lib.cbfssm_backward_pass_bwd_in_f64(*a, seg0, seg1, nchunk, _ptr(sa), _ptr(sk), cols,
+                                                         _ptr(self.in_bufs[1]), st), 'cbfssm_backward_pass_bwd_in_f64')
+        elif chunk is None:
             self._check(lib.cbfssm_backward_pass_bwd_f32(*a, st) if self.f32 else lib.cbfssm_backward_pass_bwd_f64(*a, st),
                         'backward_pass_bwd')
         else:
             seg0, seg1, sa, sk, cols = chunk
             _l.check(lib.cbfssm_backward_pass_bwd_ex_f64(*a, seg0, seg1, 1, _ptr(sa), _ptr(sk), cols, st),
                      'cbfssm_backward_pass_bwd_ex_f64')
+
+    def input_grads(self, grad_u, grad_y, st):
+        """d loss / d u, d loss / d y from the buffers the `_in` adjoints filled (cbfssm_input_grads_f64)"""
+        ws, (gin_f, gin_b, gyo) = self.ws, self.in_bufs
+        _l.check(_l.load().cbfssm_input_grads_f64(C.byref(self.prob), C.byref(self.pack_f.layout), _ptr(self.pack_f.buf),
+                                                  C.byref(self.pack_b.layout), _ptr(self.pack_b.buf), _ptr(self.var_y),
+                                                  _ptr(self.y), _ptr(ws.x), _ptr(gin_f), _ptr(gin_b), _ptr(gyo), self.cL,
+                                                  _ptr(grad_u), _ptr(grad_y), st), 'cbfssm_input_grads_f64')
 
     def half_forward_pass(self, q, st):
         lib = _l.load()

@@ -297,10 +297,12 @@ class HipElboGrad:
             self._ws[key] = ws
         return self._ws[key]
 
-    def loss_and_grads(self, params, u, y, noise, condition=True, weight=1.0, local=False):
+    def loss_and_grads(self, params, u, y, noise, condition=True, weight=1.0, local=False, input_grads=False):
         """params: dict of unconstrained float64 device tensors.  Returns (loss 0-d tensor, grads dict, terms).
-        `weight`, `local`: as in forward()."""
-        s = self._grads_local(params, u, y, noise, condition)
+        `weight`, `local`: as in forward().  input_grads: the grads also hold 'u' (B,T,dim_u) and 'y' (B,T,dim_y), the
+        gradient of the loss with respect to the input and output sequences (tf.gradients(loss, sample_in / sample_out));
+        float64 engines without a process group only."""
+        s = self._grads_local(params, u, y, noise, condition, input_grads=input_grads)
         if not local:
             self._grads_collective(s, weight)
         return self._grads_finish(s)
@@ -315,23 +317,50 @@ class HipElboGrad:
             all_reduce_sum(self.red, self.dist)     # the ONE collective of a train step (RCCL over xGMI); in stash mode
                                                     # the contracted K^-1-adjoint images ride in the same buffer
 
-    def _grads_local(self, params, u, y, noise, condition=True):
+    def _need_input_grads(self):
+        if self.f32:
+            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) exist for float64 engines only: the '
+                                      'float32 adjoint kernel keeps no data rows of the input adjoint')
+        if self.dist is not None:
+            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) are not available under a process '
+                                      'group: evaluate the shard on an engine without one')
+
+    def _input_buffers(self, prob, ws):
+        """per-chain buffers of the `_in` adjoints and the two results, kept with the workspace"""
+        if getattr(ws, 'in_bufs', None) is None:
+            lib = _l.load()
+            f = dict(dtype=torch.float64, device=self.device)
+            n = [int(fn(C.byref(prob))) for fn in (lib.cbfssm_input_adjoint_fwd_elems, lib.cbfssm_input_adjoint_bwd_elems,
+                                                   lib.cbfssm_input_adjoint_obs_elems)]
+            assert min(n) >= 0, n
+            ws.in_bufs = tuple(torch.zeros(max(k, 1), **f) for k in n)
+            ws.grad_u = torch.zeros(prob.B, prob.T, prob.dim_u, **f)
+            ws.grad_y = torch.zeros(prob.B, prob.T, prob.dim_y, **f)
+        return ws.in_bufs
+
+    def _grads_local(self, params, u, y, noise, condition=True, input_grads=False):
         self._need_adjoint()
+        if input_grads:
+            self._need_input_grads()
         u, y, prob, pflat, p, c = self._prepare(params, u, y, condition)
         self.last_ws = ws = self._workspace(prob)
         lp = self._loops(prob, ws, c, u, y, noise)
+        if input_grads:
+            lp.in_bufs = self._input_buffers(prob, ws)
         self._elbo_forward(lp)
         # ---- adjoint time loops
         if self.stash and not self.f32:
             gB_f, gB_b = self._adjoint_stash(lp, self.red)
         else:
             gB_f, gB_b = self._adjoint(lp, self.red)
+        if input_grads:
+            lp.input_grads(ws.grad_u, ws.grad_y, _stream())
         # ---- data scalars and the log-likelihood's pull on var_y (cbfssm.py:245-251)
         sf, sb = self.slab_f, self.slab_b
         tail = self.red[sf + sb:sf + sb + self.ntail]
         _l.check(_l.load().cbfssm_data_tail_f64(C.byref(prob), _ptr(c['var_y']), _ptr(ws.ll_part), _ptr(ws.out), lp.cL,
                                           _ptr(tail), _stream()), 'cbfssm_data_tail_f64')
-        return dict(ws=ws, p=p, c=c, pflat=pflat, gB_f=gB_f, gB_b=gB_b, cL=lp.cL, cE=lp.cE)
+        return dict(ws=ws, p=p, c=c, pflat=pflat, gB_f=gB_f, gB_b=gB_b, cL=lp.cL, cE=lp.cE, input_grads=bool(input_grads))
 
     def _grads_finish(self, s):
         lib = _l.load()
@@ -355,7 +384,10 @@ class HipElboGrad:
                                              _ptr(gB_b), 0, g_mode(self.f32, self.pack_f.layout), _ptr(pflat),
                                              _ptr(self.cflat), _ptr(self.tail_work), _ptr(self.gflat), st)
             _l.check(rc, 'cbfssm_train_tail_g_f64')
-            return loss, _flat_views(self.gflat, self.pl, self.dim_u), terms
+            grads = _flat_views(self.gflat, self.pl, self.dim_u)
+            if s.get('input_grads'):
+                grads['u'], grads['y'] = ws.grad_u, ws.grad_y
+            return loss, grads, terms
 
         # ---- once-per-step adjoints and the chain through the positivity transforms (tensor-library restatement)
         grads = {}
@@ -378,6 +410,8 @@ class HipElboGrad:
         gvy[:self.dim_y] += tail[3:]
         grads['var_x_unc'] = gvx * torch.sigmoid(p['var_x_unc'])
         grads['var_y_unc'] = gvy * torch.sigmoid(p['var_y_unc'])
+        if s.get('input_grads'):
+            grads['u'], grads['y'] = ws.grad_u, ws.grad_y
 
         return loss, grads, terms
 

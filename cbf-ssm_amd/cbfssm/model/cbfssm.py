@@ -18,7 +18,10 @@ from .session import Fetch, Saver, InvalidArgumentError, OutOfRangeError
 from ..synthetic import softplus_inverse
 
 _FETCHES = ('train', 'loss', 'pred_mean', 'pred_var', 'internal_mean', 'internal_var', 'mse', 'sde',
-            'loglik', 'kl_x', 'entropy', 'kl_z_f', 'kl_z_b', 'x_final', 'y_tilde')
+            'loglik', 'kl_x', 'entropy', 'kl_z_f', 'kl_z_b', 'x_final', 'y_tilde',
+            # tf.gradients(model.loss, model.sample_in / model.sample_out) for the loaded mini-batch: (B, T, dim_u / dim_y)
+            'grad_sample_in', 'grad_sample_out')
+_INPUT_GRAD_FETCHES = ('grad_sample_in', 'grad_sample_out')
 
 
 def backward(y):
@@ -256,6 +259,14 @@ class CBFSSM(BaseModel):
         if 'condition' not in feed:
             raise KeyError('feed_dict must set model.condition (cbfssm.py:227)')
         condition = bool(feed['condition'])
+        want_in = any(n in _INPUT_GRAD_FETCHES for n in names)
+        if want_in:                               # refused before a mini-batch is taken from the iterator
+            from ..hip.train import HipElboGrad
+            if type(self._engine) is not HipElboGrad:
+                raise NotImplementedError('%s has no input gradients: the recognition kernels of the forward-only variants '
+                                          'return none (grad_sample_in / grad_sample_out are CBFSSM fetches)'
+                                          % type(self).__name__)
+            self._engine._need_input_grads()      # float32 engines, process groups
         u, y = self._device_batch()
         # Data parallel: runs that fetch only the loss (and `train`) shard the mini-batch over the ranks and exchange one
         # all-reduce; runs that fetch per-sequence results (pred_mean, x_final, ...) are evaluated whole on every rank,
@@ -275,7 +286,15 @@ class CBFSSM(BaseModel):
         B, T = u.shape[0], u.shape[1]
         noise = self._draw_noise(B, T, common=(self._dist is not None and not sharded))
         eng = self._engine
-        if 'train' in names:
+        in_grads = None
+        if want_in:
+            # the eager path: the input-gradient adjoint is not part of the captured train step
+            loss, grads, terms = eng.loss_and_grads(self._opt.views, u, y, noise, condition, input_grads=True)
+            in_grads = {'grad_sample_in': grads['u'], 'grad_sample_out': grads['y']}
+            if 'train' in names:
+                self._opt.step(grads)                                                                 # cbfssm.py:275
+            ws = eng.last_ws
+        elif 'train' in names:
             stepper = self._train_stepper()
             if stepper is not None:                       # loss, gradient and Adam update as HIP graph replays
                 loss = stepper.step(u, y, noise, condition, **kw)
@@ -297,9 +316,9 @@ class CBFSSM(BaseModel):
             assert all(n in self._SCALAR_FETCHES for n in names)
             return row
         host = row.cpu().numpy()
-        return self._scalar_results(names, host, ws, y, B, T)
+        return self._scalar_results(names, host, ws, y, B, T, in_grads)
 
-    def _scalar_results(self, names, host, ws=None, y=None, B=None, T=None):
+    def _scalar_results(self, names, host, ws=None, y=None, B=None, T=None, in_grads=None):
         """host = [info, loss, scalars in _SCALAR_FETCHES order...] of one run -> the fetched values"""
         scal_names = [k for k in ('loglik', 'kl_x', 'entropy', 'kl_z_f', 'kl_z_b') if k in names]
         info, loss_h = float(host[0]), float(host[1])
@@ -327,6 +346,8 @@ class CBFSSM(BaseModel):
             elif n == 'y_tilde':                                                                      # cbfssm.py:95-97
                 y2 = ws.y2.view(T, B, S, self.dim_x - self.dim_y).permute(1, 0, 2, 3)
                 out.append(torch.cat((y[:, :, None, :].expand(B, T, S, self.dim_y), y2), dim=3).cpu().numpy())
+            elif n in _INPUT_GRAD_FETCHES:
+                out.append(in_grads[n].cpu().numpy())
             else:
                 raise KeyError(n)
         return out

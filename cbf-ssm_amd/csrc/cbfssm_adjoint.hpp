@@ -72,6 +72,9 @@ struct RevArgs {
     const double* fmv;     // (fmean, fvar) of every step as saved by the forward evaluation (PassArgs::fmv layout)
     int ksave;             // 1: every saved record is [A2 tile][kernel tile] (PassArgs::ksave)
     int M;                 // inducing points (rows m >= M of the tiles are padding)
+    // input gradients (the IG instantiations only): per step and chain, written once by the workgroup that owns them
+    double* gin;           // fwd: (T-1, dim_u, N), bwd: (2, T, dim_u+dim_y, N): adjoint of the scaled data rows x~[j] of the GP input
+    double* gyo;           // fwd: (T, dim_y, N): adjoint of the observed dimensions of y_tilde (row 0: of x_0)
 };
 
 // slab layout (doubles), all in MFMA C-layout [r][lane] blocks of 256
@@ -95,10 +98,12 @@ struct Slab {
 //     with Zbar~ the accumulator the kernel keeps anyway; the second sum is one fused multiply-add per step and lane.
 // A wave's slot of the partial tiles: JX blocks of 256, and at least the 16 x 17 transpose scratch the eight-wave tiles
 // put there (272 doubles).
-template <int DK>
+// IG (input gradients: d loss / d u and d loss / d y are wanted): the data rows j >= 16 are an output of every step, so both
+// blocks go through the MFMAs again -- the general JX = JB path, on the chain.
+template <int DK, bool IG = false>
 struct RevInGeom {
     static constexpr int JB = (4 * DK + 1 + 15) / 16;
-    static constexpr bool SPLITJ = (JB == 2);
+    static constexpr bool SPLITJ = (JB == 2) && !IG;
     static constexpr int JX = SPLITJ ? 1 : JB;
     static constexpr int PSL = SPLITJ ? 272 : (JB > 2 ? JB : 2) * 256;
     static constexpr int ECS = SPLITJ ? 16 : 0;                         // column sums of Ebar: doubles per wave
@@ -124,13 +129,13 @@ __device__ __forceinline__ double rowgroup_sum(double x)
 // LDS budget of one adjoint workgroup (doubles).  Stash-mode tiles re-read the Z~ operand images every step instead of
 // holding them in registers; when the K^-1 image does not fit anyway, the LDS left over holds those images (a read
 // that misses L1 costs an L2 round trip right in front of the MFMAs that need it).
-template <int NBLK, int RB, int DK, bool STASH>
+template <int NBLK, int RB, int DK, bool STASH, bool IG = false>
 struct RevLds {
     static constexpr int W = (NBLK + RB - 1) / RB;
     static constexpr int JB = (4 * DK + 1 + 15) / 16;
-    static constexpr int JX = RevInGeom<DK>::JX;
-    static constexpr int PSL = RevInGeom<DK>::PSL;
-    static constexpr int ECS = W * RevInGeom<DK>::ECS;
+    static constexpr int JX = RevInGeom<DK, IG>::JX;
+    static constexpr int PSL = RevInGeom<DK, IG>::PSL;
+    static constexpr int ECS = W * RevInGeom<DK, IG>::ECS;
     static constexpr int BASE_PLAIN = 2 * 4 * DK * 17 + 2 * (16 * NBLK) * 17 + 2 * 16 * 17 + W * PSL + 64 + ECS;
     // Stash-mode tiles that stream K^-1: the per-wave partial tiles of the input adjoint (`part`, written at the end of
     // phase F, read in phase G) live in the K tile's LDS, which is dead by then -- one more workgroup barrier per step
@@ -204,7 +209,10 @@ constexpr bool rev_extra_wave(int nblk, bool stash) { return stash ? (nblk != 16
 // KSV: the forward evaluation kept the kernel tile of every step next to its A2 tile (RevArgs::ksave, non-stash tiles):
 // phase B is a copy -- registers that were loaded a step ahead go to the LDS tile -- instead of 6 MFMAs and four
 // exponentials per lane, and the Z~ rows / row constants of the wave are not held at all.
-template <int NBLK, int RB, int DK, bool BLDS, bool STASH, int MODE, int KD = 4, bool KSV = false>
+// IG: the launch also writes, per step and chain, the adjoint of the data rows of the GP input (RevArgs::gin) and, in the
+// forward-pass adjoint, of the observed dimensions of y_tilde (RevArgs::gyo): what tf.gradients(loss, sample_in / sample_out)
+// needs of the time loops.  Off: the code below is the code without the switch.
+template <int NBLK, int RB, int DK, bool BLDS, bool STASH, int MODE, int KD = 4, bool KSV = false, bool IG = false>
 __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, STASH) ? 1 : 0))) void rev_kernel(RevArgs a)
 {
     static_assert(!(KSV && STASH), "kernel tiles are kept for the register-resident tile heights only");
@@ -225,10 +233,10 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
 
     extern __shared__ double lds[];
     double* xq0 = lds;                                  // [2][4*DK][17]: this step's and the next step's inputs
-    typedef RevLds<NBLK, RB, DK, STASH> RL;
+    typedef RevLds<NBLK, RB, DK, STASH, IG> RL;
     constexpr bool PALIAS = RL::PALIAS && !BLDS;        // `part` shares the K tile's LDS (see RevLds)
-    constexpr bool SPLITJ = RevInGeom<DK>::SPLITJ;      // block 1 of the input adjoint stays off the MFMAs (RevInGeom)
-    constexpr int JX = RevInGeom<DK>::JX, PSL = RevInGeom<DK>::PSL;
+    constexpr bool SPLITJ = RevInGeom<DK, IG>::SPLITJ;  // block 1 of the input adjoint stays off the MFMAs (RevInGeom)
+    constexpr int JX = RevInGeom<DK, IG>::JX, PSL = RevInGeom<DK, IG>::PSL;
     double* Kt = xq0 + 2 * 4 * DK * PD;                 // [MP][17]
     double* A2t = Kt + (PALIAS ? RL::KTR : MP * PD);    // [MP][17]
     double* Fm = A2t + MP * PD;                         // [16][17]
@@ -508,11 +516,17 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
                             gvy[qi] += gvyt;
                             gfv += kf1 * gvyt;
                             if (d >= a.dim_y && !a.half) a.gy2[(int64_t(t + 1) * N + c) * dob + (d - a.dim_y)] = gyt;
+                            if constexpr (IG) {
+                                if (d < a.dim_y) a.gyo[(int64_t(t + 1) * a.dim_y + d) * N + c] = gyt;
+                            }
                         } else {
                             // x' = fmean + eps sqrt(fvar), no KL term                           (cbfssm.py:224,234)
                             gfm = gout;
                             gfv = gout * eps_t * 0.5 * fast_rsqrt(fvar);
                             if (d >= a.dim_y && !a.half) a.gy2[(int64_t(t + 1) * N + c) * dob + (d - a.dim_y)] = 0.0;
+                            if constexpr (IG) {
+                                if (d < a.dim_y) a.gyo[(int64_t(t + 1) * a.dim_y + d) * N + c] = 0.0;
+                            }
                         }
                     } else {
                         // out = fmean + eps sqrt(fvar); entropy term on written steps          (cbfssm.py:150-156)
@@ -1215,6 +1229,11 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
                     const double xt = xq[j * PD + nl];
                     xb -= xt * esum;
                     glx[k2] += xb * xt;                                            // lengthscale adjoint (inputs)
+                    if constexpr (IG) {
+                        // data rows (u, and y in the backward runs): their adjoint leaves the kernel, scaled by 1/l later
+                        const int64_t slot = (MODE == MODE_FWD) ? int64_t(t) : (int64_t(run) * T + t);
+                        if (j >= Do) a.gin[((slot * naux) + (j - Do)) * N + c] = xb;
+                    }
                 }
                 if (!SPLITJ && j == D && cvalid) glogsig += xb;
                 // state rows hand their adjoint to the phase-D lanes of the same (d, chain): identical lanes when
@@ -1235,6 +1254,7 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
                                     if (t == 0) {
                                         if (a.half) a.gx0[int64_t(c) * a.dim_x + d] = gin;       // x_0 = recognition model
                                         else if (d >= a.dim_y) a.gy2[int64_t(c) * dob + (d - a.dim_y)] = gin;   // x_0 = y_tilde_0
+                                        else if constexpr (IG) a.gyo[int64_t(d) * N + c] = gin;
                                     }
                                 }
                                 gcar[qi] = gin;
@@ -1272,6 +1292,8 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
                         a.gx0[int64_t(c) * a.dim_x + d] = gv;
                     } else if (d >= a.dim_y) {
                         a.gy2[int64_t(c) * dob + (d - a.dim_y)] = 0.0;
+                    } else if constexpr (IG) {
+                        a.gyo[int64_t(d) * N + c] = 0.0;
                     }
                 }
             }

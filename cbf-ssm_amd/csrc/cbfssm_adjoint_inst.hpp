@@ -20,12 +20,12 @@ struct RevCfg {
     static constexpr int W = (NBLK + RB - 1) / RB;
 };
 
-template <int NBLK, int DK>
+template <int NBLK, int DK, bool IG = false>
 struct RevGeom {
     typedef RevCfg<NBLK> C;
     static constexpr int JB = (4 * DK + 1 + 15) / 16;
-    static constexpr int PSL = RevInGeom<DK>::PSL;
-    static constexpr int LDS_BASE = 2 * 4 * DK * 17 + 2 * (16 * NBLK) * 17 + 2 * 16 * 17 + C::W * PSL + 64 + C::W * RevInGeom<DK>::ECS;
+    static constexpr int PSL = RevInGeom<DK, IG>::PSL;
+    static constexpr int LDS_BASE = 2 * 4 * DK * 17 + 2 * (16 * NBLK) * 17 + 2 * 16 * 17 + C::W * PSL + 64 + C::W * RevInGeom<DK, IG>::ECS;
     static constexpr int LDS_LIMIT = 163840 / 8;
     static constexpr int SLAB = Slab<NBLK, JB, C::STASH>::total;
 };
@@ -106,6 +106,55 @@ int launch_rev_n(int DK, int mode, const RevArgs& a, dim3 grid, hipStream_t st)
     return -2;
 }
 
+// Input-gradient launches (rev_kernel<..., IG = true>, RevArgs::gin / gyo): one kernel per (tile height, input k-steps,
+// direction, K^-1 placement).  They read the saved A2 tiles when there are any and rebuild the kernel tile (no KSV / KD = 2
+// forms: this path has no speed target, and every form is a kernel to compile).
+template <int NBLK, int DK, int MODE>
+int launch_revin_k(const RevArgs& a, dim3 grid, hipStream_t st)
+{
+    typedef RevGeom<NBLK, DK, true> G;
+    typedef RevCfg<NBLK> C;
+    const int blds_doubles = NBLK * a.KSr * 64;
+    const dim3 block(64 * (C::W + (rev_extra_wave(NBLK, C::STASH) ? 1 : 0)));
+    if (G::LDS_BASE + blds_doubles <= G::LDS_LIMIT && !getenv("CBFSSM_NO_BLDS")) {
+        const size_t lds = size_t(G::LDS_BASE + blds_doubles) * sizeof(double);
+        auto k = rev_kernel<NBLK, C::RB, DK, true, C::STASH, MODE, 4, false, true>;
+        int rc = set_lds(k, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k, grid, block, lds, st, a);
+    } else {
+        typedef RevLds<NBLK, C::RB, DK, C::STASH, true> RL;
+        static_assert(RL::BASE_PLAIN == G::LDS_BASE, "LDS layout");
+        static_assert(RL::BASE + RL::EXTRA <= RL::LIMIT, "LDS budget");
+        const size_t lds = size_t(RL::BASE + RL::EXTRA) * sizeof(double);
+        auto k = rev_kernel<NBLK, C::RB, DK, false, C::STASH, MODE, 4, false, true>;
+        int rc = set_lds(k, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k, grid, block, lds, st, a);
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -int(e) - 1000;
+}
+
+template <int NBLK>
+int launch_revin_n(int DK, int mode, const RevArgs& a, dim3 grid, hipStream_t st)
+{
+    if (mode == MODE_FWD) {
+        switch (DK) {
+            case 2: return launch_revin_k<NBLK, 2, MODE_FWD>(a, grid, st);
+            case 4: return launch_revin_k<NBLK, 4, MODE_FWD>(a, grid, st);
+            case 6: return launch_revin_k<NBLK, 6, MODE_FWD>(a, grid, st);
+        }
+    } else {
+        switch (DK) {
+            case 2: return launch_revin_k<NBLK, 2, MODE_BWD>(a, grid, st);
+            case 4: return launch_revin_k<NBLK, 4, MODE_BWD>(a, grid, st);
+            case 6: return launch_revin_k<NBLK, 6, MODE_BWD>(a, grid, st);
+        }
+    }
+    return -2;
+}
+
 template <int NBLK>
 int64_t rev_slab_n(int DK)
 {
@@ -123,6 +172,19 @@ int64_t rev_slab_n(int DK)
     namespace cbfssm {                                                                           \
     int launch_rev_nb##NB(int DK, int mode, const RevArgs& a, dim3 grid, hipStream_t st);        \
     int64_t rev_slab_nb##NB(int DK);                                                             \
+    }
+
+#define CBF_REVIN_DECLARE(NB)                                                                    \
+    namespace cbfssm {                                                                           \
+    int launch_revin_nb##NB(int DK, int mode, const RevArgs& a, dim3 grid, hipStream_t st);      \
+    }
+
+#define CBF_REVIN_INSTANTIATE(NB)                                                                \
+    namespace cbfssm {                                                                           \
+    int launch_revin_nb##NB(int DK, int mode, const RevArgs& a, dim3 grid, hipStream_t st)       \
+    {                                                                                            \
+        return launch_revin_n<NB>(DK, mode, a, grid, st);                                        \
+    }                                                                                            \
     }
 
 #define CBF_REV_INSTANTIATE(NB)                                                                  \

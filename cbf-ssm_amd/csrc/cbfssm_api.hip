@@ -12,6 +12,7 @@
 
 CBF_FOR_EACH_NBLK(CBF_DECLARE)
 CBF_FOR_EACH_REV_NBLK(CBF_REV_DECLARE)
+CBF_FOR_EACH_REV_NBLK(CBF_REVIN_DECLARE)
 
 namespace cbfssm {
 
@@ -718,6 +719,65 @@ __global__ void reduce_partials_stage2(const double* tmp, int64_t slab, double* 
     out[i] = s;
 }
 
+// d loss / d u (B,T,dim_u) and d loss / d y (B,T,dim_y) from the per-chain buffers of the input-gradient adjoints: one thread
+// per output entry, the S particles of its sequence summed in particle order, then forward pass + run 0 + run 1, each
+// scaled by 1/lengthscale of its GP and input row; y also gets the observed dimensions' adjoint of y_tilde and the
+// log-likelihood's direct term (cbfssm.py:245-251).  Single pass, fixed order: bitwise reproducible.
+struct InGradArgs {
+    int B, S, T, dim_x, dim_u, dim_y;
+    const double* gin_f;   // (T-1, dim_u, N)
+    const double* gin_b;   // (2, T, dim_u + dim_y, N)
+    const double* gyo;     // (T, dim_y, N)
+    const double* invl_f;  // [D] of gp_f: data rows start at dim_x
+    const double* invl_b;  // [D] of gp_b: data rows start at dim_x - dim_y
+    const double* x;       // (T, N, dim_x)
+    const double* y;       // (B, T, dim_y)
+    const double* var_y;
+    double cL;
+    double* gu;
+    double* gy;
+};
+
+__global__ void input_grads_kernel(InGradArgs a)
+{
+    const int64_t nu = int64_t(a.B) * a.T * a.dim_u, ny = int64_t(a.B) * a.T * a.dim_y;
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= nu + ny) return;
+    const int64_t N = int64_t(a.B) * a.S;
+    const int naux = a.dim_u + a.dim_y, dob = a.dim_x - a.dim_y;
+    const bool is_u = i < nu;
+    const int nd = is_u ? a.dim_u : a.dim_y;
+    const int64_t e = is_u ? i : i - nu;
+    const int k = int(e % nd);
+    const int t = int((e / nd) % a.T);
+    const int b = int(e / (int64_t(nd) * a.T));
+    const int ja = is_u ? k : a.dim_u + k;                      // data row of the backward GP's input
+    const double* p0 = a.gin_b + ((int64_t(0) * a.T + t) * naux + ja) * N + int64_t(b) * a.S;
+    const double* p1 = a.gin_b + ((int64_t(1) * a.T + t) * naux + ja) * N + int64_t(b) * a.S;
+    double s0 = 0.0, s1 = 0.0;
+    for (int s = 0; s < a.S; ++s) { s0 += p0[s]; s1 += p1[s]; }
+    double r = a.invl_b[dob + ja] * (s0 + s1);
+    if (is_u) {
+        if (t < a.T - 1) {
+            const double* pf = a.gin_f + (int64_t(t) * a.dim_u + k) * N + int64_t(b) * a.S;
+            double sf = 0.0;
+            for (int s = 0; s < a.S; ++s) sf += pf[s];
+            r += a.invl_f[a.dim_x + k] * sf;
+        }
+        a.gu[e] = r;
+    } else {
+        const double* po = a.gyo + (int64_t(t) * a.dim_y + k) * N + int64_t(b) * a.S;
+        const double* px = a.x + (int64_t(t) * N + int64_t(b) * a.S) * a.dim_x + k;
+        const double yv = a.y[e];
+        double so = 0.0, sl = 0.0;
+        for (int s = 0; s < a.S; ++s) {
+            so += po[s];
+            sl += yv - px[int64_t(s) * a.dim_x];
+        }
+        a.gy[e] = r + so + a.cL * sl / a.var_y[k];
+    }
+}
+
 __global__ void reduce_partials_kernel(const double* gpart, int64_t slab, int nwg, double* out)
 {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -764,6 +824,16 @@ static int dispatch_rev(int NBLK, int DK, int mode, const RevArgs& a, dim3 grid,
 {
     switch (NBLK) {
 #define X(NB) case NB: return launch_rev_nb##NB(DK, mode, a, grid, st);
+        CBF_FOR_EACH_REV_NBLK(X)
+#undef X
+    }
+    return -3;
+}
+
+static int dispatch_revin(int NBLK, int DK, int mode, const RevArgs& a, dim3 grid, hipStream_t st)
+{
+    switch (NBLK) {
+#define X(NB) case NB: return launch_revin_nb##NB(DK, mode, a, grid, st);
         CBF_FOR_EACH_REV_NBLK(X)
 #undef X
     }
@@ -1295,7 +1365,8 @@ static int forward_pass_bwd_impl(const cbfssm_problem* p, const cbfssm_pack_layo
                                  const double* y2, const double* eps_f, const double* x, const double* fmv_f,
                                  const double* a2s_f, double cL, double* gy2,
                                  double* gx0, double* gpart, int t_hi, int t_lo, double* gx_carry, double* stash_a,
-                                 double* stash_k, int64_t stash_ld, void* stream)
+                                 double* stash_k, int64_t stash_ld, void* stream, double* gin_f = nullptr,
+                                 double* gyo = nullptr, bool input_grads = false)
 {
     int rc = check_problem(p, L, p ? p->dim_x : 0);
     if (rc) return rc;
@@ -1311,6 +1382,11 @@ static int forward_pass_bwd_impl(const cbfssm_problem* p, const cbfssm_pack_layo
     a.cL = cL; a.var_x = var_x; a.var_y = var_y; a.u = u; a.y = y; a.eps = eps_f; a.x = x; a.y2 = y2; a.gy2 = gy2;
     a.gpart = gpart; a.t_hi = t_hi; a.t_lo = t_lo; a.gx_carry = gx_carry;
     a.half = p->half; a.gx0 = gx0;
+    if (input_grads) {
+        if (p->half) return fail(-1, "input gradients: not for the forward-only variants");
+        if ((p->dim_u > 0 && p->T > 1 && !gin_f) || (p->dim_y > 0 && !gyo)) return fail(-1, "gin_f/gyo is null");
+        a.gin = gin_f; a.gyo = gyo;
+    }
     a.fmv = fmv_f;
     a.a2s = a2s_f;
     a.ksave = a2s_f ? save_k(L) : 0;
@@ -1323,7 +1399,8 @@ static int forward_pass_bwd_impl(const cbfssm_problem* p, const cbfssm_pack_layo
     if (rc) return rc;
     a.group0 = g0; a.gtotal = gt;
     dim3 grid(unsigned(ng), 1);
-    rc = dispatch_rev(L->NBLK, L->DK, MODE_FWD, a, grid, (hipStream_t)stream);
+    rc = input_grads ? dispatch_revin(L->NBLK, L->DK, MODE_FWD, a, grid, (hipStream_t)stream)
+                     : dispatch_rev(L->NBLK, L->DK, MODE_FWD, a, grid, (hipStream_t)stream);
     if (rc) return fail(rc, "forward_pass_bwd launch failed (NBLK=%d DK=%d rc=%d)", L->NBLK, L->DK, rc);
     return 0;
 }
@@ -1337,6 +1414,18 @@ int cbfssm_forward_pass_bwd_ex_f64(const cbfssm_problem* p, const cbfssm_pack_la
     if (p && p->half) return fail(-1, "problem->half is set: use cbfssm_half_forward_pass_bwd_f64");
     return forward_pass_bwd_impl(p, L, pack_f, var_x, var_y, u, y, y2, eps_f, x, fmv_f, a2s_f, cL, gy2, nullptr, gpart,
                                  t_hi, t_lo, gx_carry, stash_a, stash_k, stash_ld, stream);
+}
+
+int cbfssm_forward_pass_bwd_in_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_f,
+                                   const double* var_x, const double* var_y, const double* u, const double* y,
+                                   const double* y2, const double* eps_f, const double* x, const double* fmv_f,
+                                   const double* a2s_f, double cL, double* gy2, double* gpart, int t_hi, int t_lo,
+                                   double* gx_carry, double* stash_a, double* stash_k, int64_t stash_ld, double* gin_f,
+                                   double* gyo, void* stream)
+{
+    if (p && p->half) return fail(-1, "problem->half is set: the forward-only variants have no input gradients");
+    return forward_pass_bwd_impl(p, L, pack_f, var_x, var_y, u, y, y2, eps_f, x, fmv_f, a2s_f, cL, gy2, nullptr, gpart,
+                                 t_hi, t_lo, gx_carry, stash_a, stash_k, stash_ld, stream, gin_f, gyo, true);
 }
 
 int cbfssm_half_forward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_f,
@@ -1360,11 +1449,11 @@ int cbfssm_forward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_layou
                                           p ? p->T - 2 : -1, 0, nullptr, nullptr, nullptr, 0, stream);
 }
 
-int cbfssm_backward_pass_bwd_ex_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_b,
-                                    const double* var_x, const double* u, const double* y, const double* hid_b,
-                                    const double* eps_b, const double* h_all, const double* fmv_b, const double* a2s_b,
-                                    const double* gy2, double cE, double* gpart, int seg0, int seg1, int nchunk, double* stash_a,
-                                    double* stash_k, int64_t stash_ld, void* stream)
+static int backward_pass_bwd_impl(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_b,
+                                  const double* var_x, const double* u, const double* y, const double* hid_b,
+                                  const double* eps_b, const double* h_all, const double* fmv_b, const double* a2s_b,
+                                  const double* gy2, double cE, double* gpart, int seg0, int seg1, int nchunk, double* stash_a,
+                                  double* stash_k, int64_t stash_ld, void* stream, double* gin_b, bool input_grads)
 {
     int rc = check_problem(p, L, p ? p->dim_x - p->dim_y : 0);
     if (rc) return rc;
@@ -1377,6 +1466,11 @@ int cbfssm_backward_pass_bwd_ex_f64(const cbfssm_problem* p, const cbfssm_pack_l
     if (rc) return rc;
     a.cE = cE; a.var_x = var_x; a.u = u; a.y = y; a.eps = eps_b; a.hid = hid_b; a.h_all = h_all;
     a.gy2 = const_cast<double*>(gy2); a.gpart = gpart;
+    if (input_grads) {
+        if (p->half) return fail(-1, "input gradients: not for the forward-only variants");
+        if (p->dim_u + p->dim_y > 0 && !gin_b) return fail(-1, "gin_b is null");
+        a.gin = gin_b;
+    }
     a.fmv = fmv_b;
     a.a2s = a2s_b;
     a.ksave = a2s_b ? save_k(L) : 0;
@@ -1390,9 +1484,76 @@ int cbfssm_backward_pass_bwd_ex_f64(const cbfssm_problem* p, const cbfssm_pack_l
     if (rc) return rc;
     a.group0 = g0; a.gtotal = gt;
     dim3 grid(unsigned(ng), 2, unsigned(nchunk));
-    rc = dispatch_rev(L->NBLK, L->DK, MODE_BWD, a, grid, (hipStream_t)stream);
+    rc = input_grads ? dispatch_revin(L->NBLK, L->DK, MODE_BWD, a, grid, (hipStream_t)stream)
+                     : dispatch_rev(L->NBLK, L->DK, MODE_BWD, a, grid, (hipStream_t)stream);
     if (rc) return fail(rc, "backward_pass_bwd launch failed (NBLK=%d DK=%d rc=%d)", L->NBLK, L->DK, rc);
     return 0;
+}
+
+int cbfssm_backward_pass_bwd_ex_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_b,
+                                    const double* var_x, const double* u, const double* y, const double* hid_b,
+                                    const double* eps_b, const double* h_all, const double* fmv_b, const double* a2s_b,
+                                    const double* gy2, double cE, double* gpart, int seg0, int seg1, int nchunk, double* stash_a,
+                                    double* stash_k, int64_t stash_ld, void* stream)
+{
+    return backward_pass_bwd_impl(p, L, pack_b, var_x, u, y, hid_b, eps_b, h_all, fmv_b, a2s_b, gy2, cE, gpart, seg0, seg1,
+                                  nchunk, stash_a, stash_k, stash_ld, stream, nullptr, false);
+}
+
+int cbfssm_backward_pass_bwd_in_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_b,
+                                    const double* var_x, const double* u, const double* y, const double* hid_b,
+                                    const double* eps_b, const double* h_all, const double* fmv_b, const double* a2s_b,
+                                    const double* gy2, double cE, double* gpart, int seg0, int seg1, int nchunk, double* stash_a,
+                                    double* stash_k, int64_t stash_ld, double* gin_b, void* stream)
+{
+    return backward_pass_bwd_impl(p, L, pack_b, var_x, u, y, hid_b, eps_b, h_all, fmv_b, a2s_b, gy2, cE, gpart, seg0, seg1,
+                                  nchunk, stash_a, stash_k, stash_ld, stream, gin_b, true);
+}
+
+static int input_dims_ok(const cbfssm_problem* p)
+{
+    return p && p->B >= 1 && p->S >= 1 && p->T >= 1 && p->dim_u >= 0 && p->dim_y >= 0 && p->dim_y <= p->dim_x;
+}
+
+int64_t cbfssm_input_adjoint_fwd_elems(const cbfssm_problem* p)
+{
+    if (!input_dims_ok(p)) return -1;
+    return int64_t(p->T - 1) * p->dim_u * p->B * p->S;
+}
+
+int64_t cbfssm_input_adjoint_bwd_elems(const cbfssm_problem* p)
+{
+    if (!input_dims_ok(p)) return -1;
+    return int64_t(2) * p->T * (p->dim_u + p->dim_y) * p->B * p->S;
+}
+
+int64_t cbfssm_input_adjoint_obs_elems(const cbfssm_problem* p)
+{
+    if (!input_dims_ok(p)) return -1;
+    return int64_t(p->T) * p->dim_y * p->B * p->S;
+}
+
+int cbfssm_input_grads_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_f, const double* pack_f,
+                           const cbfssm_pack_layout* layout_b, const double* pack_b, const double* var_y, const double* y,
+                           const double* x, const double* gin_f, const double* gin_b, const double* gyo, double cL,
+                           double* grad_u, double* grad_y, void* stream)
+{
+    int rc = check_problem(p, layout_f, p ? p->dim_x : 0);
+    if (rc) return rc;
+    rc = check_problem(p, layout_b, p->dim_x - p->dim_y);
+    if (rc) return rc;
+    if (p->half) return fail(-1, "input gradients: not for the forward-only variants");
+    if (!pack_f || !pack_b || !var_y || !y || !x || !gin_b) return fail(-1, "null pointer");
+    if ((p->dim_u > 0 && (!grad_u || (p->T > 1 && !gin_f))) || (p->dim_y > 0 && (!grad_y || !gyo))) return fail(-1, "null pointer");
+    InGradArgs a;
+    a.B = p->B; a.S = p->S; a.T = p->T; a.dim_x = p->dim_x; a.dim_u = p->dim_u; a.dim_y = p->dim_y;
+    a.gin_f = gin_f; a.gin_b = gin_b; a.gyo = gyo;
+    a.invl_f = pack_f + layout_f->invl; a.invl_b = pack_b + layout_b->invl;
+    a.x = x; a.y = y; a.var_y = var_y; a.cL = cL; a.gu = grad_u; a.gy = grad_y;
+    const int64_t total = int64_t(p->B) * p->T * (p->dim_u + p->dim_y);
+    if (total <= 0) return 0;
+    hipLaunchKernelGGL(input_grads_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("input_grads");
 }
 
 int cbfssm_backward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_b,

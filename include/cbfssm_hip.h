@@ -289,6 +289,46 @@ int cbfssm_backward_pass_bwd_ex_f64(const cbfssm_problem* p, const cbfssm_pack_l
                                     const double* gy2, double cE, double* gpart, int seg0, int seg1, int nchunk,
                                     double* stash_a, double* stash_k, int64_t stash_ld, void* stream);
 
+/*
+ * ---- input gradients: d loss / d u (B,T,dim_u) and d loss / d y (B,T,dim_y).  Replaces tf.gradients(model.loss,
+ * model.sample_in) and tf.gradients(model.loss, model.sample_out), i.e. the gradient of the loss with respect to the
+ * placeholders of base_model.py:22-27, which the reference's graph gives for free (cbfssm/model/voliro.py:106-137 trains
+ * through it).  CBFSSM, float64 only.
+ *
+ * The `_in` forms of the two adjoint passes take the arguments of the `_ex` forms plus per-chain output buffers, and run
+ * instantiations of the adjoint kernel that multiply every 16-row block of the input adjoint again (the default ones keep
+ * only the state rows).  The parameter slabs are written as by the `_ex` forms (same layout; the lengthscale adjoint of the
+ * input rows j >= 16 is accumulated per step instead of rebuilt, so it agrees to rounding, not bitwise).  Every launch
+ * writes the entries of its own time range and chain groups only; entries of padded chains do not exist.
+ *   gin_f (cbfssm_input_adjoint_fwd_elems doubles, (T-1, dim_u, N)): adjoint of the scaled u rows of gp_f's input, steps 0 .. T-2
+ *   gyo   (cbfssm_input_adjoint_obs_elems doubles, (T, dim_y, N)):   adjoint of the observed dimensions of y_tilde[t]
+ *                                                                    (t = 0: of x_0 = y_tilde[0])
+ *   gin_b (cbfssm_input_adjoint_bwd_elems doubles, (2, T, dim_u+dim_y, N)): adjoint of the scaled u and y rows of gp_b's
+ *                                                                    input, per run and step (both runs evaluate gp_b at every t)
+ * cbfssm_input_grads_f64: one launch, after both adjoints are complete: sums the S particles of a sequence in particle
+ * order, then forward pass + run 0 + run 1, scales each row by 1/lengthscale of its GP and row (from the packs), and adds
+ * to d loss / d y the log-likelihood's direct term cL sum_s (y - x) / var_y (cbfssm.py:245-251; x: the trajectory
+ * cbfssm_loglik_moments_f64 reads).  Fixed order, no atomics: two evaluations are bitwise identical.
+ */
+int64_t cbfssm_input_adjoint_fwd_elems(const cbfssm_problem* p);
+int64_t cbfssm_input_adjoint_bwd_elems(const cbfssm_problem* p);
+int64_t cbfssm_input_adjoint_obs_elems(const cbfssm_problem* p);
+int cbfssm_forward_pass_bwd_in_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_f, const double* pack_f,
+                                   const double* var_x, const double* var_y, const double* u, const double* y,
+                                   const double* y2, const double* eps_f, const double* x, const double* fmv_f,
+                                   const double* a2s_f, double cL, double* gy2, double* gpart, int t_hi, int t_lo,
+                                   double* gx_carry, double* stash_a, double* stash_k, int64_t stash_ld, double* gin_f,
+                                   double* gyo, void* stream);
+int cbfssm_backward_pass_bwd_in_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_b, const double* pack_b,
+                                    const double* var_x, const double* u, const double* y, const double* hid_b,
+                                    const double* eps_b, const double* h_all, const double* fmv_b, const double* a2s_b,
+                                    const double* gy2, double cE, double* gpart, int seg0, int seg1, int nchunk,
+                                    double* stash_a, double* stash_k, int64_t stash_ld, double* gin_b, void* stream);
+int cbfssm_input_grads_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_f, const double* pack_f,
+                           const cbfssm_pack_layout* layout_b, const double* pack_b, const double* var_y, const double* y,
+                           const double* x, const double* gin_f, const double* gin_b, const double* gyo, double cL,
+                           double* grad_u, double* grad_y, void* stream);
+
 /* out[i] = sum over the nwg slabs, in a fixed order (bitwise reproducible).  gpart must have room for
  * nwg + CBFSSM_REDUCE_SPLIT slabs: the tail is scratch for the first of the two reduction stages. */
 #define CBFSSM_REDUCE_SPLIT 32
