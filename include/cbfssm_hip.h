@@ -488,6 +488,9 @@ int cbfssm_train_tail_half_f64(const cbfssm_pack_layout* layout, const double* p
  * The backward call takes d loss / d x_0 per sequence (the adjoint pass's gx0 summed over the particles) and writes one
  * gradient slab of cbfssm_gru_recog_param_elems doubles per sequence (gpart: room for B + CBFSSM_REDUCE_SPLIT slabs);
  * cbfssm_reduce_partials_f64(gpart, elems, B, out) sums them in a fixed order.
+ * The two counts are host arithmetic: -1 for dim_u < 0, dim_y < 1, dim_x < 1, B < 1 or recog_len < 1, and no upper limit.
+ * Limits of the compute entry points, decided on the host before anything is launched: 1 <= recog_len <= T, dim_y >= 1
+ * (else -1); dim_u + dim_y <= 32, dim_x <= 16 (else -3).  u may be NULL when dim_u = 0.
  */
 int64_t cbfssm_gru_recog_param_elems(int dim_u, int dim_y, int dim_x);
 int64_t cbfssm_gru_recog_act_elems(int B, int recog_len);
