@@ -1,4 +1,7 @@
-"""The CBF-SSM loss as a differentiable torch function over the HIP engine.
+"""Differentiable torch functions over the HIP library: the CBF-SSM loss of a whole engine (`elbo_loss`) and the two
+functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down).
+
+The CBF-SSM loss:
 
     loss = elbo_loss(engine, params, u, y, noise, condition=True)
 
@@ -15,8 +18,13 @@ process group) are computed only when u or y requires grad, or when `input_grads
 `input_grads=False` the call is the engine's default adjoint and u, y receive no gradient.  Nothing here computes on
 the host or in the tensor library: a missing kernel is the engine's error.
 """
-import torch
+import ctypes as C
 
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import lib as _l
+from .ops import _ptr, _stream, tf_forward
 from .train import PARAM_NAMES
 
 
@@ -54,3 +62,136 @@ def elbo_loss(engine, params, u, y, noise, condition=True, input_grads=None):
     if input_grads is False and (getattr(u, 'requires_grad', False) or getattr(y, 'requires_grad', False)):
         u, y = u.detach(), y.detach()
     return _ElboLoss.apply(engine, bool(condition), noise, input_grads, u, y, *[params[k] for k in PARAM_NAMES])
+
+
+# ---- one sparse GP: GPModel.predict and GPModel.prior_kl (gp_tf.py:132-172) as torch functions -------------------------
+#
+#     fmean, fvar = gp_predict(pack, X, zeta_pos, zeta_mean, zeta_var_unc, variance_unc, lengthscales_unc)
+#     kl = gp_prior_kl(pack, zeta_pos, zeta_mean, zeta_var_unc, variance_unc, lengthscales_unc)
+#
+# `pack` is an ops.GPPack of the right (M, D, Do); the five parameter tensors are the UNCONSTRAINED leaves (GPModel.parameters()),
+# X is (npts, D); everything float64 on the pack's device.  The forward calls prepare the pack and evaluate as the
+# evaluation-only path does; backward of gp_predict is cbfssm_gp_predict_bwd_f64 -> cbfssm_reduce_partials_f64 ->
+# cbfssm_gp_tail_f64 with kl_weight 0, backward of gp_prior_kl is cbfssm_gp_tail_f64 without a slab and kl_weight 1, scaled by
+# the incoming scalar on the device.  Nothing synchronises with the host.  The pack is shared and mutable (the next
+# prepare overwrites it), so each call keeps a copy of the prepared buffer for its backward (0.3 MB at M = 100).  Once
+# differentiable: the backward kernels are not themselves differentiated.
+
+GP_PARAM_NAMES = ('zeta_pos', 'zeta_mean', 'zeta_var_unc', 'variance_unc', 'lengthscales_unc')
+
+
+def _gp_flat(params):
+    """(pflat, cflat): the five tensors behind each other, unconstrained and constrained (cbfssm_gp_tail_f64's order)."""
+    zp, zm, zv, var, ls = [p.detach().reshape(-1) for p in params]
+    pflat = torch.cat([zp, zm, zv, var, ls]).contiguous()
+    cflat = torch.cat([zp, zm, tf_forward(zv), tf_forward(var), tf_forward(ls)]).contiguous()
+    return pflat, cflat
+
+
+def _gp_prepare(pack, params, cflat):
+    M, D, Do = pack.M, pack.D, pack.Do
+    assert tuple(params[0].shape) == (M, D) and tuple(params[1].shape) == (M, Do) and tuple(params[2].shape) == (M, Do)
+    assert params[3].numel() == 1 and params[4].numel() == D
+    o1, o2, o3, o4 = M * D, M * D + M * Do, M * D + 2 * M * Do, M * D + 2 * M * Do + 1
+    pack.prepare(cflat[:o1].view(M, D), cflat[o4:], cflat[o3:o4], cflat[o1:o2].view(M, Do), cflat[o2:o3].view(M, Do))
+
+
+def _gp_tail(layout, buf, red, image, kl_weight, pflat, cflat):
+    lib = _l.load()
+    work = torch.empty(int(lib.cbfssm_train_tail_half_work_elems(C.byref(layout))), dtype=torch.float64, device=buf.device)
+    gflat = torch.empty_like(pflat)
+    _l.check(lib.cbfssm_gp_tail_f64(C.byref(layout), _ptr(buf), _ptr(red), _ptr(image), 0, float(kl_weight), _ptr(pflat),
+                                    _ptr(cflat), _ptr(work), _ptr(gflat), _stream()), 'cbfssm_gp_tail_f64')
+    return gflat
+
+
+def _gp_split(gflat, shapes, need):
+    out, o = [], 0
+    for s, nd in zip(shapes, need):
+        n = 1
+        for k in s:
+            n *= k
+        out.append(gflat[o:o + n].view(s) if nd else None)
+        o += n
+    return tuple(out)
+
+
+class _GpPredict(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, X, *params):
+        pflat, cflat = _gp_flat(params)
+        _gp_prepare(pack, params, cflat)
+        Xd = X.detach().contiguous()
+        fmean, fvar = pack.predict(Xd)
+        ctx.layout, ctx.buf = pack.layout, pack.buf.clone()
+        ctx.X, ctx.pflat, ctx.cflat = Xd, pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in params)
+        return fmean, fvar
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gmean, gvar):
+        lib = _l.load()
+        lay, buf, X = ctx.layout, ctx.buf, ctx.X
+        need = ctx.needs_input_grad
+        n, dev = X.shape[0], X.device
+        need_p = any(need[2:])
+        gX = torch.empty_like(X)
+        if n == 0:
+            gp = _gp_split(torch.zeros_like(ctx.pflat), ctx.shapes, need[2:])
+            return (None, gX if need[1] else None) + gp
+        gmean, gvar = gmean.contiguous(), gvar.contiguous()
+        nwg = int(lib.cbfssm_gp_predict_bwd_workgroups(C.byref(lay), n))
+        nwork = int(lib.cbfssm_gp_predict_bwd_work_elems(C.byref(lay), n))
+        if nwg < 1 or nwork < 0:
+            raise _l.CbfssmHipError('cbfssm_gp_predict_bwd_workgroups / _work_elems refused the layout')
+        gpart = torch.empty((nwg + 32) * lay.rev_slab, dtype=torch.float64, device=dev)     # (+ CBFSSM_REDUCE_SPLIT)
+        work = torch.empty(nwork, dtype=torch.float64, device=dev) if nwork else None
+        image = torch.empty(lay.NBLK * lay.NBLK * 256, dtype=torch.float64, device=dev) if lay.rev_stash else None
+        _l.check(lib.cbfssm_gp_predict_bwd_f64(C.byref(lay), _ptr(buf), _ptr(X), n, _ptr(gmean), _ptr(gvar), _ptr(gX),
+                                               _ptr(gpart), _ptr(work), _ptr(image), _stream()), 'cbfssm_gp_predict_bwd_f64')
+        gp = (None,) * 5
+        if need_p:
+            red = torch.empty(lay.rev_slab, dtype=torch.float64, device=dev)
+            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), lay.rev_slab, nwg, _ptr(red), _stream()),
+                     'cbfssm_reduce_partials_f64')
+            gp = _gp_split(_gp_tail(lay, buf, red, image, 0.0, ctx.pflat, ctx.cflat), ctx.shapes, need[2:])
+        return (None, gX if need[1] else None) + gp
+
+
+class _GpPriorKl(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, *params):
+        pflat, cflat = _gp_flat(params)
+        _gp_prepare(pack, params, cflat)
+        ctx.layout, ctx.buf = pack.layout, pack.buf.clone()
+        ctx.pflat, ctx.cflat = pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in params)
+        return pack.scal[_l.SCAL_KLZ].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        gflat = _gp_tail(ctx.layout, ctx.buf, None, None, 1.0, ctx.pflat, ctx.cflat) * gout
+        return (None,) + _gp_split(gflat, ctx.shapes, ctx.needs_input_grad[1:])
+
+
+def _gp_args(pack, params):
+    if len(params) != 5:
+        raise TypeError('expected the five tensors %s' % ', '.join(GP_PARAM_NAMES))
+    dev = pack.buf.device
+    return [torch.as_tensor(p, dtype=torch.float64, device=dev) for p in params]
+
+
+def gp_predict(pack, X, *params):
+    """GPModel.predict(X) -> (fmean (npts, Do), fvar (npts, Do)) with a grad_fn into X and the five parameter tensors."""
+    X = torch.as_tensor(X, dtype=torch.float64, device=pack.buf.device)
+    assert X.dim() == 2 and X.shape[1] == pack.D
+    return _GpPredict.apply(pack, X, *_gp_args(pack, params))
+
+
+def gp_prior_kl(pack, *params):
+    """GPModel.prior_kl() as a 0-d tensor with a grad_fn into the five parameter tensors."""
+    return _GpPriorKl.apply(pack, *_gp_args(pack, params))

@@ -29,6 +29,7 @@ SYMBOLS = (
     'cbfssm_saved_a2_f32_elems', 'cbfssm_half_forward_pass_f32', 'cbfssm_half_forward_pass_bwd_f32', 'cbfssm_rev32_slab_elems', 'cbfssm_normal_f64', 'cbfssm_philox4x32_10_u32', 'cbfssm_forward_pass_bwd_f32', 'cbfssm_backward_pass_bwd_f32',
     'cbfssm_input_adjoint_fwd_elems', 'cbfssm_input_adjoint_bwd_elems', 'cbfssm_input_adjoint_obs_elems',
     'cbfssm_forward_pass_bwd_in_f64', 'cbfssm_backward_pass_bwd_in_f64', 'cbfssm_input_grads_f64',
+    'cbfssm_gp_predict_bwd_workgroups', 'cbfssm_gp_predict_bwd_work_elems', 'cbfssm_gp_predict_bwd_f64', 'cbfssm_gp_tail_f64',
 )
 
 
@@ -153,6 +154,11 @@ def load():
     lib.cbfssm_forward_pass_bwd_in_f64.argtypes = ([C.POINTER(Problem), C.POINTER(PackLayout)] + [vp] * 10 + [dbl, vp, vp, ip, ip, vp, vp, vp, i64, vp, vp, vp])
     lib.cbfssm_backward_pass_bwd_in_f64.argtypes = ([C.POINTER(Problem), C.POINTER(PackLayout)] + [vp] * 10 + [dbl, vp, ip, ip, ip, vp, vp, i64, vp, vp])
     lib.cbfssm_input_grads_f64.argtypes = [C.POINTER(Problem), C.POINTER(PackLayout), vp, C.POINTER(PackLayout), vp] + [vp] * 6 + [dbl, vp, vp, vp]
+    for name in ('cbfssm_gp_predict_bwd_workgroups', 'cbfssm_gp_predict_bwd_work_elems'):
+        getattr(lib, name).restype = i64
+        getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]
+    lib.cbfssm_gp_predict_bwd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.cbfssm_gp_tail_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, dbl, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith('_elems'):                 # element counts: 64-bit results (set above)

@@ -9,6 +9,12 @@ stand-alone surface of the same kernels, for callers that hold GP objects rather
     cast_cholesky(mat, jitter=1e-8)                    gp_tf.py:52-65  (float64 whatever the input dtype)
     conditional(Xnew, X, kern, f, q_sqrt, Lm=None)     gp_tf.py:68-100 (q_sqrt None, (M, Do) or (Do, M, M))
     GPModel(in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var)      gp_tf.py:103-172
+
+GPModel is differentiable: when one of its five leaf tensors (`GPModel.parameters()`) or `Xnew` requires grad, `predict`
+and `prior_kl` return tensors with a grad_fn (cbfssm.hip.autograd.gp_predict / gp_prior_kl: hand-written adjoint kernels,
+no tensor-library fallback), so a model built around a sparse GP -- the reference's Voliro pattern, gp_f.predict plus a
+physics term (cbfssm/model/voliro.py:106-123) -- trains with torch.optim.  Without a gradient request both are the
+evaluation-only calls they always were.
 """
 import ctypes as C
 import numpy as np
@@ -105,7 +111,8 @@ def conditional(Xnew, X, kern, f, q_sqrt, Lm=None):
     """GPflow-1.0-style conditional (gp_tf.py:68-100): p(f* | q(f) = N(f, q_sqrt q_sqrt^T)), unwhitened.
     q_sqrt: None, (M, Do) standard deviations, or (Do, M, M) lower-triangular factors.  `Lm` is accepted for signature
     compatibility; the factor is recomputed from (X, kern) on the device (it is what Lm must equal, gp_tf.py:71-72).
-    Returns (fmean (N, Do), fvar (N, Do))."""
+    Returns (fmean (N, Do), fvar (N, Do)).  Evaluation only: the results carry no grad_fn whatever the arguments require
+    (the differentiable surface is GPModel.predict / prior_kl)."""
     dev = kern.device
     X, Xnew, f = _f64(X, dev), _f64(Xnew, dev), _f64(f, dev)
     M, Do = f.shape
@@ -133,7 +140,9 @@ def conditional(Xnew, X, kern, f, q_sqrt, Lm=None):
 
 class GPModel:
     """Sparse GP with diagonal q(z) (gp_tf.py:103-172): inducing inputs / means drawn as the reference draws them
-    (unseeded unless `seed` is given), `predict(Xnew)` and `prior_kl()` on the device."""
+    (unseeded unless `seed` is given), `predict(Xnew)` and `prior_kl()` on the device.  The five tensors of `parameters()`
+    are leaves: set `requires_grad_()` on them (or hand `predict` an `Xnew` that requires grad) and both calls are
+    differentiable; see the module docstring."""
 
     def __init__(self, in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var, dtype='float64',
                  device=None, seed=None):
@@ -162,8 +171,21 @@ class GPModel:
     def cholesky(self):
         return self._prepared().L.clone()                                                                        # :129-130
 
+    def parameters(self):
+        """The five trainable leaves, in the order of cbfssm.hip.autograd.GP_PARAM_NAMES."""
+        return [self.zeta_pos, self.zeta_mean, self.zeta_var_unc, self.kern.variance_unc, self.kern.lengthscales_unc]
+
+    def _wants_grad(self, *more):
+        return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in self.parameters() + list(more))
+
     def predict(self, Xnew):
+        if self._wants_grad(Xnew):
+            from ..hip import autograd as _ag
+            return _ag.gp_predict(self._pack, Xnew, *self.parameters())
         return self._prepared().predict(Xnew)                                                                    # :132-161
 
     def prior_kl(self):
+        if self._wants_grad():
+            from ..hip import autograd as _ag
+            return _ag.gp_prior_kl(self._pack, *self.parameters())
         return self._prepared().scal[_l.SCAL_KLZ].clone()                                                        # :163-172

@@ -46,6 +46,8 @@ struct GpTail {
                               // part itself, K^-1 (d loss / d K^-1) K^-1 (float32 adjoint, cbfssm_rev32.hip) -- 1: the full
                               // matrix, 2: only its lower-triangular 16 x 16 blocks, as S = C A2^T + A2 C^T (diagonal blocks:
                               // C A2^T); either way only the symmetric part of G enters
+    double klw;               // weight of the prior-KL terms (gp_tf.py:163-172): 1 in a train step, the caller's in cbfssm_gp_tail_f64
+    int nodata;               // 1: there is no slab (cbfssm_gp_tail_f64 with red_slab = NULL): the data terms read as zero
 };
 
 struct TailArgs {
@@ -83,6 +85,7 @@ __device__ __forceinline__ double block_sum_t(double v, double* red, int tid, in
 // the data part's image, element (k, j)
 __device__ __forceinline__ double img_elem(const GpTail& p, int k, int j)
 {
+    if (p.nodata) return 0.0;
     if (p.gB_dense) return (p.gB_ld > 0) ? p.gB_dense[int64_t(k) * p.gB_ld + j] : c_image(p.gB_dense, p.NBLK, k, j);
     return c_image(p.slab + 2 * p.NBLK * 256, p.NBLK, k, j);
 }
@@ -114,7 +117,7 @@ __device__ __forceinline__ double g_elem(const GpTail& p, int k, int j)
     for (int d = 0; d < p.Do; ++d) dot = fma(p.zmean[k * p.Do + d], p.zmean[j * p.Do + d], dot);
     if (k == j)
         for (int d = 0; d < p.Do; ++d) dot += p.zvar[k * p.Do + d];
-    return v + 0.5 * dot;
+    return v + p.klw * (0.5 * dot);
 }
 
 // STAGE 0: T = Kinv G.   STAGE 1: G2 = (-T Kinv + 0.5 Do Kinv) o Kmm   (K^-1 = (K_mm + jitter I)^-1, log det of the KL)
@@ -218,14 +221,14 @@ __global__ __launch_bounds__(256) void tail_gemm(TailArgs a)
                 acc += gs;
                 if (i == j) tdiag += p.scal[CBFSSM_SCAL_JITTER] * gs;
             }
-            p.G2[int64_t(i) * M + j] = (-acc + 0.5 * p.Do * kinv) * p.Kmm[int64_t(i) * M + j];
+            p.G2[int64_t(i) * M + j] = (-acc + p.klw * 0.5 * p.Do * kinv) * p.Kmm[int64_t(i) * M + j];
             // d loss / d sigma^2 needs sum_ij Kbar_ij K_mm,ij = tr(Kbar K_mm).  Summing the entries of G2 cancels twice
             // (entries of K^-1 G K^-1 are of order cond^2 |G|): with K^-1 K_mm = I - jitter K^-1 the same trace is
             //     -tr(T) + jitter tr(T K^-1) + 0.5 Do (M - jitter tr K^-1),
             // whose terms are of order cond |G| only (measured on a trained-like K_mm with cond 3e7: 3.5e-2 -> see DESIGN).
             if (i == j) {
                 const double jit = p.scal[CBFSSM_SCAL_JITTER];
-                p.dv[i] = -tdiag + jit * acc + 0.5 * p.Do * (1.0 - jit * kinv);
+                p.dv[i] = -tdiag + jit * acc + p.klw * 0.5 * p.Do * (1.0 - jit * kinv);
             }
         }
     }
@@ -245,6 +248,7 @@ __global__ __launch_bounds__(256) void tail_finish(TailArgs a)
     const double* gZ = p.slab + 2 * NBLK * 256 + (p.stash ? 0 : NBLK * NBLK * 256);
     const double* small = gZ + NBLK * JB * 256;
     const double* G2 = p.G2;
+    const bool nd = p.nodata != 0;                       // (no slab: every read of it below is replaced by zero)
 
     // K = var exp(-0.5 d2(z~)): Kbar o K = G2;  Wd = -0.5 G2, Ws = Wd + Wd^T                           (gp_tf.py:33-49)
     const double* WZ = p.T;                              // Ws z~   [M][D]     (tail_gemm<2>)
@@ -266,7 +270,8 @@ __global__ __launch_bounds__(256) void tail_finish(TailArgs a)
     for (int idx = tid; idx < M * D; idx += NT) {
         const int i = idx / D, j = idx - i * D;
         const double zs = p.Zs[idx];
-        const double gzt = c_image(gZ, JB, i, j) - zs * c_image(gZ, JB, i, D) + 2.0 * (wsrow[i] * zs - WZ[idx]);
+        const double gz0 = nd ? 0.0 : c_image(gZ, JB, i, j), gz1 = nd ? 0.0 : c_image(gZ, JB, i, D);
+        const double gzt = gz0 - zs * gz1 + 2.0 * (wsrow[i] * zs - WZ[idx]);
         p.g_z[idx] = gzt / p.ls[p.shared_ls ? 0 : j];
     }
     __syncthreads();
@@ -275,8 +280,9 @@ __global__ __launch_bounds__(256) void tail_finish(TailArgs a)
         for (int i = l; i < M; i += 64) s += p.g_z[i * D + j] * p.Zs[i * D + j];      // = Z~bar o z~ / ls
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
         if (l == 0) {
-            if (p.shared_ls) glsj[j] = -(s + small[32 + j] / p.ls[0]);
-            else p.g_ls[j] = -(s + small[32 + j] / p.ls[j]) * sigmoid(p.ls_unc[j]);
+            const double sx = nd ? 0.0 : small[32 + j];
+            if (p.shared_ls) glsj[j] = -(s + sx / p.ls[0]);
+            else p.g_ls[j] = -(s + sx / p.ls[j]) * sigmoid(p.ls_unc[j]);
         }
     }
     if (p.shared_ls) {                                   // one lengthscale: its adjoint is the sum over the input dimensions
@@ -289,13 +295,15 @@ __global__ __launch_bounds__(256) void tail_finish(TailArgs a)
     }
     if (tid == 0) {
         const double var = p.var[0];
-        p.g_var[0] = (tot / var + small[96] + small[97] / var) * sigmoid(p.var_unc[0]);
+        const double s96 = nd ? 0.0 : small[96], s97 = nd ? 0.0 : small[97];
+        p.g_var[0] = (tot / var + s96 + s97 / var) * sigmoid(p.var_unc[0]);
     }
     // inducing mean / variance: data part from the slab + prior KL                                    (gp_tf.py:163-172)
     for (int idx = tid; idx < M * Do; idx += NT) {
         const int i = idx / Do, d = idx - i * Do;
-        p.g_mu[idx] = c_image(gMu, 1, i, d) + KM[idx];
-        const double gs2 = c_image(gS2, 1, i, d) + 0.5 * ((p.Kkl ? p.Kkl : p.Kinv)[int64_t(i) * M + i] - 1.0 / p.zvar[idx]);
+        const double gm0 = nd ? 0.0 : c_image(gMu, 1, i, d), gs0 = nd ? 0.0 : c_image(gS2, 1, i, d);
+        p.g_mu[idx] = gm0 + p.klw * KM[idx];
+        const double gs2 = gs0 + p.klw * 0.5 * ((p.Kkl ? p.Kkl : p.Kinv)[int64_t(i) * M + i] - 1.0 / p.zvar[idx]);
         p.g_s2[idx] = gs2 * sigmoid(p.zvar_unc[idx]);
     }
     // process / observation noise (workgroup of gp_f): per-dimension sums of both slabs + the log-likelihood's pull
@@ -370,6 +378,58 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, double* p, const d
     m[i] = mi;
     v[i] = vi;
     p[i] -= lr_t * mi / (sqrt(vi) + eps);
+}
+
+}  // namespace cbfssm
+
+namespace cbfssm {
+
+// The tail of ONE GP (cbfssm_train_tail_half_f64, cbfssm_gp_tail_f64; arguments checked by the callers).  dim_y = 0: the flat
+// vectors end behind the lengthscales (no var_x / var_y) and `slab` may be NULL (the prior-KL terms alone).
+static int one_gp_tail(const cbfssm_pack_layout* L, const double* pack, const double* pack_kl, int shared_ls, const double* slab,
+                       const double* gB_dense, int64_t gB_ld, int g_mode, double klw, int dim_y, const double* pflat,
+                       const double* cflat, double* work, double* gflat, void* stream, const char* what)
+{
+    TailArgs a;
+    memset(&a, 0, sizeof(a));
+    GpTail& p = a.gp[0];
+    const int M = L->M, D = L->D, Do = L->Do;
+    p.slab = slab;
+    p.gB_dense = gB_dense; p.gB_ld = gB_ld;
+    p.Kinv = pack + L->Kinv; p.Kmm = pack + L->Kmm; p.Zs = pack + L->Zs;
+    double* w = work;
+    p.T = w; w += int64_t(M) * (M > 48 ? M : 48);
+    p.G2 = w; w += int64_t(M) * M;
+    p.T2 = w; w += int64_t(M) * M;
+    p.dv = w;
+    p.scal = pack + L->scal;
+    p.Kkl = pack_kl ? pack_kl + L->Kinv : nullptr;
+    p.shared_ls = shared_ls ? 1 : 0;
+    p.klw = klw; p.nodata = slab ? 0 : 1;
+    // flat layout: zeta_pos [M][D] | zeta_mean [M][Do] | zeta_var(_unc) [M][Do] | variance(_unc) [1] | lengthscales(_unc)
+    // [D or 1] | var_x(_unc) [Do] | var_y(_unc) [dim_y]
+    const int64_t o1 = int64_t(M) * D, o2 = o1 + int64_t(M) * Do, o3 = o2 + int64_t(M) * Do, o4 = o3 + 1,
+                  o5 = o4 + (shared_ls ? 1 : D), o6 = o5 + Do;
+    p.zmean = cflat + o1; p.zvar = cflat + o2; p.var = cflat + o3; p.ls = cflat + o4;
+    p.zvar_unc = pflat + o2; p.var_unc = pflat + o3; p.ls_unc = pflat + o4;
+    p.g_z = gflat; p.g_mu = gflat + o1; p.g_s2 = gflat + o2; p.g_var = gflat + o3; p.g_ls = gflat + o4;
+    p.M = M; p.D = D; p.Do = Do; p.NBLK = L->NBLK; p.JB = L->JB; p.stash = L->rev_stash; p.gmode = g_mode;
+    a.ngp = 1;
+    if (dim_y > 0) {
+        a.tail = slab + L->rev_slab;
+        a.vx_unc = pflat + o5; a.vy_unc = pflat + o6;
+        a.g_vx = gflat + o5; a.g_vy = gflat + o6;
+        a.dim_x = Do; a.dim_y = dim_y; a.n_vy = dim_y;
+    }
+    const unsigned nb = unsigned((M + 15) / 16);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(tail_gemm<0>, dim3(nb, nb, 1), dim3(16, 16), 0, st, a);
+    if (pack_kl) hipLaunchKernelGGL(tail_gemm<3>, dim3(nb, nb, 1), dim3(16, 16), 0, st, a);
+    hipLaunchKernelGGL(tail_gemm<1>, dim3(nb, nb, 1), dim3(16, 16), 0, st, a);
+    hipLaunchKernelGGL(tail_gemm<2>, dim3(3, nb, 1), dim3(16, 16), 0, st, a);
+    hipLaunchKernelGGL(tail_finish, dim3(1), dim3(256), 0, st, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(-int(e) - 1000, "%s", what);
 }
 
 }  // namespace cbfssm
@@ -472,6 +532,7 @@ int cbfssm_train_tail_g_f64(const cbfssm_param_layout* pl, const cbfssm_pack_lay
         p.M = M; p.D = L[g]->D; p.Do = L[g]->Do; p.NBLK = L[g]->NBLK; p.JB = L[g]->JB; p.stash = L[g]->rev_stash;
         p.gmode = g_mode;
         p.Kkl = nullptr; p.T2 = nullptr; p.shared_ls = 0;
+        p.klw = 1.0; p.nodata = 0;
     }
     a.ngp = 2; a.n_vy = pl->dim_x;
     a.tail = slab;
@@ -504,42 +565,23 @@ int cbfssm_train_tail_half_f64(const cbfssm_pack_layout* L, const double* pack, 
     if (L->M > 320 || L->D > 32) return fail(-3, "tail kernel limits: M <= 320, D <= 32");
     if ((L->rev_stash != 0) != (gB_dense != nullptr)) return fail(-1, "the dense K^-1 adjoint is required exactly in stash mode");
     if (dim_y < 1 || dim_y > L->Do) return fail(-1, "bad dim_y");
-    TailArgs a;
-    memset(&a, 0, sizeof(a));
-    GpTail& p = a.gp[0];
-    const int M = L->M, D = L->D, Do = L->Do;
-    p.slab = red;
-    p.gB_dense = gB_dense; p.gB_ld = gB_ld;
-    p.Kinv = pack + L->Kinv; p.Kmm = pack + L->Kmm; p.Zs = pack + L->Zs;
-    double* w = work;
-    p.T = w; w += int64_t(M) * (M > 48 ? M : 48);
-    p.G2 = w; w += int64_t(M) * M;
-    p.T2 = w; w += int64_t(M) * M;
-    p.dv = w;
-    p.scal = pack + L->scal;
-    p.Kkl = pack_kl ? pack_kl + L->Kinv : nullptr;
-    p.shared_ls = shared_ls ? 1 : 0;
-    // flat layout: zeta_pos [M][D] | zeta_mean [M][Do] | zeta_var(_unc) [M][Do] | variance(_unc) [1] | lengthscales(_unc)
-    // [D or 1] | var_x(_unc) [Do] | var_y(_unc) [dim_y]
-    const int64_t o1 = int64_t(M) * D, o2 = o1 + int64_t(M) * Do, o3 = o2 + int64_t(M) * Do, o4 = o3 + 1,
-                  o5 = o4 + (shared_ls ? 1 : D), o6 = o5 + Do;
-    p.zmean = cflat + o1; p.zvar = cflat + o2; p.var = cflat + o3; p.ls = cflat + o4;
-    p.zvar_unc = pflat + o2; p.var_unc = pflat + o3; p.ls_unc = pflat + o4;
-    p.g_z = gflat; p.g_mu = gflat + o1; p.g_s2 = gflat + o2; p.g_var = gflat + o3; p.g_ls = gflat + o4;
-    p.M = M; p.D = D; p.Do = Do; p.NBLK = L->NBLK; p.JB = L->JB; p.stash = L->rev_stash; p.gmode = g_mode;
-    a.tail = red + L->rev_slab;
-    a.vx_unc = pflat + o5; a.vy_unc = pflat + o6;
-    a.g_vx = gflat + o5; a.g_vy = gflat + o6;
-    a.dim_x = Do; a.dim_y = dim_y; a.ngp = 1; a.n_vy = dim_y;
-    const unsigned nb = unsigned((M + 15) / 16);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(tail_gemm<0>, dim3(nb, nb, 1), dim3(16, 16), 0, st, a);
-    if (pack_kl) hipLaunchKernelGGL(tail_gemm<3>, dim3(nb, nb, 1), dim3(16, 16), 0, st, a);
-    hipLaunchKernelGGL(tail_gemm<1>, dim3(nb, nb, 1), dim3(16, 16), 0, st, a);
-    hipLaunchKernelGGL(tail_gemm<2>, dim3(3, nb, 1), dim3(16, 16), 0, st, a);
-    hipLaunchKernelGGL(tail_finish, dim3(1), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(-int(e) - 1000, "train tail (forward-only variant) launch failed");
+    return one_gp_tail(L, pack, pack_kl, shared_ls, red, gB_dense, gB_ld, g_mode, 1.0, dim_y, pflat, cflat, work, gflat, stream,
+                       "train tail (forward-only variant) launch failed");
+}
+
+int cbfssm_gp_tail_f64(const cbfssm_pack_layout* L, const double* pack, const double* red_slab, const double* gB_dense,
+                       int64_t gB_ld, double kl_weight, const double* pflat, const double* cflat, double* work, double* gflat,
+                       void* stream)
+{
+    if (!L || !pack || !pflat || !cflat || !work || !gflat) return fail(-1, "null pointer");
+    if (L->rev_slab <= 0) return fail(-3, "no adjoint slab for M=%d", L->M);
+    if (L->M < 1 || L->M > 320 || L->D < 1 || L->D > 32 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT)
+        return fail(-3, "tail kernel limits: M <= 320, D <= 32, Do <= %d", CBFSSM_MAX_DOUT);
+    if (red_slab && (L->rev_stash != 0) != (gB_dense != nullptr))
+        return fail(-1, "the dense K^-1 adjoint is required exactly in stash mode");
+    if (!red_slab && gB_dense) return fail(-1, "a K^-1 adjoint without a slab");
+    return one_gp_tail(L, pack, nullptr, 0, red_slab, gB_dense, gB_ld, 0, kl_weight, 0, pflat, cflat, work, gflat, stream,
+                       "gp tail launch failed");
 }
 
 int cbfssm_data_tail_f64(const cbfssm_problem* p, const double* var_y, const double* ll_part, const double* out8, double cL,

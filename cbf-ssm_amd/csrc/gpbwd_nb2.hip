@@ -1,0 +1,2 @@
+#include "cbfssm_gp_bwd.hpp"
+CBF_GPBWD_INSTANTIATE(2)

@@ -148,6 +148,40 @@ int cbfssm_gp_predict_fullq_f64(const cbfssm_pack_layout* layout, const double* 
                                 int64_t npts, double* fmean, double* fvar, double* work, void* stream);
 
 /*
+ * ---- differentiable GPModel: what tf.gradients gives a graph that calls gp.predict / gp.prior_kl outside a CBF-SSM
+ * (gp_tf.py:132-172 differentiated; cbfssm/model/voliro.py:106-123 calls gp_f.predict once over all B T points).
+ *
+ * cbfssm_gp_predict_bwd_f64: batch adjoint of cbfssm_gp_predict_f64 (gp_tf.py:132-161).  pack: prepared with the
+ * parameters of the forward call; X (npts, D); gmean, gvar (npts, Do): d loss / d fmean, d loss / d fvar.
+ *   -> gX (npts, D): d loss / d X (the unscaled inputs), every entry written exactly once;
+ *      gpart: cbfssm_gp_predict_bwd_workgroups partial slabs of layout->rev_slab doubles in the slab layout of the
+ *      time-loop adjoints below ("Slab layout of the parameter adjoints of one GP"; the var_x / var_y entries are zero), with
+ *      room for CBFSSM_REDUCE_SPLIT more: cbfssm_reduce_partials_f64(gpart, layout->rev_slab, workgroups, red) sums them;
+ *      M > 112 (layout->rev_stash): the slab has no d/dK^-1 section; the call writes the MFMA operand images of
+ *      d loss / d K^-1 += A2bar K^T per 16-point block to `work` (cbfssm_gp_predict_bwd_work_elems doubles) and
+ *      contracts them (cbfssm_stash_contract_f64) into gB_image, [NBLK][NBLK][4][64] doubles, which it clears first:
+ *      hand it to cbfssm_gp_tail_f64 as gB_dense with gB_ld = 0.  M <= 112: work and gB_image may be NULL.
+ * Both GP forms (layout->gp_form) have this adjoint: it is evaluated with the K^-1 contraction.  No atomics; two calls are
+ * bitwise identical.  Limits as cbfssm_gp_predict_f64 (M <= 320, D <= 24, Do <= 16), else -3 before any launch; the two
+ * counts are host arithmetic and return -1 for a bad layout or npts < 0.
+ *
+ * cbfssm_gp_tail_f64: adjoint of GPModel.__init__ / prior_kl (gp_tf.py:33-65,129-130,163-172) and the chain through the
+ * positivity transforms for ONE GP: d (data loss + kl_weight * prior_kl) / d parameters.  Flat vectors (pflat unconstrained,
+ * cflat constrained, gflat the gradient) in the order zeta_pos [M][D] | zeta_mean [M][Do] | zeta_var [M][Do] | variance [1] |
+ * lengthscales [D].  red_slab: the reduced slab, or NULL for the prior-KL terms alone (gB_dense then NULL too); gB_dense /
+ * gB_ld as in cbfssm_train_tail_f64.  work: cbfssm_train_tail_half_work_elems doubles.  (cbfssm_train_tail_half_f64 is the
+ * same with kl_weight = 1 and the var_x / var_y entries behind.)
+ */
+int64_t cbfssm_gp_predict_bwd_workgroups(const cbfssm_pack_layout* layout, int64_t npts);
+int64_t cbfssm_gp_predict_bwd_work_elems(const cbfssm_pack_layout* layout, int64_t npts);
+int cbfssm_gp_predict_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* X, int64_t npts,
+                              const double* gmean, const double* gvar, double* gX, double* gpart, double* work,
+                              double* gB_image, void* stream);
+int cbfssm_gp_tail_f64(const cbfssm_pack_layout* layout, const double* pack, const double* red_slab, const double* gB_dense,
+                       int64_t gB_ld, double kl_weight, const double* pflat, const double* cflat, double* work, double* gflat,
+                       void* stream);
+
+/*
  * Both backward (recognition) runs, CBFSSM._backward/_backward_run/_backward_body (cbfssm.py:84-158).
  *   u (B,T,dim_u), y (B,T,dim_y), hid_b (2,T,N), eps_b (2,T,N), var_x (dim_x)
  *   -> y2 (T,N,dim_x-dim_y)  [every t written by exactly one run, cbfssm.py:123-128,151]
