@@ -1,5 +1,5 @@
-"""Differentiable torch functions over the HIP library: the CBF-SSM loss of a whole engine (`elbo_loss`) and the two
-functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down).
+"""Differentiable torch functions over the HIP library: the CBF-SSM loss of a whole engine (`elbo_loss`), the two
+functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down) and its recurrence over time (`gp_rollout`, at the end).
 
 The CBF-SSM loss:
 
@@ -195,3 +195,135 @@ def gp_predict(pack, X, *params):
 def gp_prior_kl(pack, *params):
     """GPModel.prior_kl() as a 0-d tensor with a grad_fn into the five parameter tensors."""
     return _GpPriorKl.apply(pack, *_gp_args(pack, params))
+
+
+# ---- the recurrence of one sparse GP: h <- h + gp(h, a_t) + eps_t sqrt(fvar + var_add) over time, one launch ------------
+#
+#     traj, entropy = gp_rollout(pack, h0, a, eps, var_add, zeta_pos, zeta_mean, zeta_var_unc, variance_unc, lengthscales_unc,
+#                                reverse=False)
+#
+# h0 (N, Do), a (T, N, Da) with Da = D - Do (None or (T, N, 0) when Da = 0), eps (T, N) standard normals, var_add (Do)
+# CONSTRAINED values or None; traj (T, N, Do) time-major, entropy = 0.5 sum log(2 pi e (fvar + var_add)) a 0-d tensor.
+# Voliro's recognition run (cbfssm/model/voliro.py:139-186) is reverse=True from h0 = 0 with a = (u_t, y_t) per particle;
+# the free-running transition of a trained CBF-SSM (cbfssm/model/cbfssm.py:199-206,224) is reverse=False with a = u_t.
+# Forward: cbfssm_gp_rollout_f64, the entropy partials summed in a fixed order by cbfssm_reduce_partials_f64.  Backward:
+# cbfssm_gp_rollout_bwd_f64 -> cbfssm_reduce_partials_f64 -> cbfssm_gp_tail_f64 (kl_weight 0); gradients for h0, a, var_add
+# and the five parameter tensors, none for eps.  Once differentiable, no host synchronisation; the call keeps a copy of the
+# prepared pack, as gp_predict does.
+
+def _rollout_forward(lay, buf, h0, a, eps, var_add, reverse, save):
+    """(traj, vsave or None, entropy) of one forward launch on prepared pack operands"""
+    lib = _l.load()
+    T, N = eps.shape
+    Do, dev = lay.Do, buf.device
+    if T < 1:
+        raise ValueError('gp_rollout: at least one time step')
+    traj = torch.empty(T, N, Do, dtype=torch.float64, device=dev)
+    vsave = torch.empty_like(traj) if save else None
+    if N == 0:
+        return traj, vsave, torch.zeros((), dtype=torch.float64, device=dev)
+    npart = int(lib.cbfssm_gp_rollout_partials(C.byref(lay), N))
+    if npart < 1:
+        raise _l.CbfssmHipError('cbfssm_gp_rollout_partials refused the layout')
+    ent_part = torch.empty(npart + 32, dtype=torch.float64, device=dev)                     # (+ CBFSSM_REDUCE_SPLIT)
+    _l.check(lib.cbfssm_gp_rollout_f64(C.byref(lay), _ptr(buf), _ptr(h0), _ptr(a), _ptr(eps), _ptr(var_add), N, T,
+                                       int(bool(reverse)), _ptr(traj), _ptr(vsave), _ptr(ent_part), _stream()),
+             'cbfssm_gp_rollout_f64')
+    ent = torch.empty(1, dtype=torch.float64, device=dev)
+    _l.check(lib.cbfssm_reduce_partials_f64(_ptr(ent_part), 1, npart, _ptr(ent), _stream()), 'cbfssm_reduce_partials_f64')
+    return traj, vsave, ent.reshape(())
+
+
+def _rollout_args(pack, h0, a, eps, var_add):
+    dev = pack.buf.device
+    Do, Da = pack.Do, pack.D - pack.Do
+    if Da < 0:
+        raise ValueError('gp_rollout: the GP input dimension %d is smaller than its output dimension %d' % (pack.D, pack.Do))
+    eps = torch.as_tensor(eps, dtype=torch.float64, device=dev)
+    h0 = torch.as_tensor(h0, dtype=torch.float64, device=dev)
+    assert eps.dim() == 2 and h0.dim() == 2 and h0.shape == (eps.shape[1], Do), 'eps (T, N), h0 (N, Do)'
+    T, N = eps.shape
+    if Da == 0:
+        assert a is None or tuple(a.shape) == (T, N, 0), 'a: None or (T, N, 0) when the GP takes the state alone'
+        a = None
+    else:
+        a = torch.as_tensor(a, dtype=torch.float64, device=dev)
+        assert tuple(a.shape) == (T, N, Da), 'a (T, N, D - Do)'
+    if var_add is not None:
+        var_add = torch.as_tensor(var_add, dtype=torch.float64, device=dev)
+        assert var_add.shape == (Do,), 'var_add (Do)'
+    return h0, a, eps, var_add
+
+
+class _GpRollout(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, reverse, h0, a, eps, var_add, *params):
+        pflat, cflat = _gp_flat(params)
+        _gp_prepare(pack, params, cflat)
+        h0d, epsd = h0.detach().contiguous(), eps.detach().contiguous()
+        ad = a.detach().contiguous() if a is not None else None
+        vad = var_add.detach().contiguous() if var_add is not None else None
+        buf = pack.buf.clone()
+        traj, vsave, ent = _rollout_forward(pack.layout, buf, h0d, ad, epsd, vad, reverse, True)
+        ctx.layout, ctx.buf, ctx.reverse = pack.layout, buf, bool(reverse)
+        ctx.has_a = ad is not None
+        ctx.save_for_backward(h0d, epsd, traj, vsave, *([ad] if ad is not None else []))     # (traj is an output)
+        ctx.pflat, ctx.cflat = pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in params)
+        return traj, ent
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gtraj, gent):
+        lib = _l.load()
+        lay, buf = ctx.layout, ctx.buf
+        h0, eps, traj, vsave = ctx.saved_tensors[:4]
+        a = ctx.saved_tensors[4] if ctx.has_a else None
+        need = ctx.needs_input_grad
+        T, N = eps.shape
+        dev = eps.device
+        gh0 = torch.empty_like(h0)
+        ga = torch.empty_like(a) if a is not None else None
+        if N == 0:
+            gp = _gp_split(torch.zeros_like(ctx.pflat), ctx.shapes, need[6:])
+            gva = torch.zeros(lay.Do, dtype=torch.float64, device=dev) if need[5] else None
+            return (None, None, gh0 if need[2] else None, ga if need[3] else None, None, gva) + gp
+        gtraj = gtraj.contiguous()
+        gent = gent.reshape(1).contiguous()
+        nwg = int(lib.cbfssm_gp_rollout_bwd_workgroups(C.byref(lay), N))
+        nwork = int(lib.cbfssm_gp_rollout_bwd_work_elems(C.byref(lay), N, T))
+        if nwg < 1 or nwork < 0:
+            raise _l.CbfssmHipError('cbfssm_gp_rollout_bwd_workgroups / _work_elems refused the layout')
+        gpart = torch.empty((nwg + 32) * lay.rev_slab, dtype=torch.float64, device=dev)     # (+ CBFSSM_REDUCE_SPLIT)
+        work = torch.empty(nwork, dtype=torch.float64, device=dev) if nwork else None
+        image = torch.empty(lay.NBLK * lay.NBLK * 256, dtype=torch.float64, device=dev) if lay.rev_stash else None
+        _l.check(lib.cbfssm_gp_rollout_bwd_f64(C.byref(lay), _ptr(buf), _ptr(h0), _ptr(a), _ptr(eps), _ptr(traj), _ptr(vsave),
+                                               _ptr(gtraj), _ptr(gent), N, T, int(ctx.reverse), _ptr(gh0), _ptr(ga),
+                                               _ptr(gpart), _ptr(work), _ptr(image), _stream()), 'cbfssm_gp_rollout_bwd_f64')
+        gp, gva = (None,) * 5, None
+        if need[5] or any(need[6:]):
+            red = torch.empty(lay.rev_slab, dtype=torch.float64, device=dev)
+            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), lay.rev_slab, nwg, _ptr(red), _stream()),
+                     'cbfssm_reduce_partials_f64')
+            if need[5]:
+                small = lay.rev_slab - 192                  # the slab's scalars: [0, 16) d/d var_x by state dim
+                gva = red[small:small + lay.Do].clone()
+            if any(need[6:]):
+                gp = _gp_split(_gp_tail(lay, buf, red, image, 0.0, ctx.pflat, ctx.cflat), ctx.shapes, need[6:])
+        return (None, None, gh0 if need[2] else None, ga if need[3] else None, None, gva) + gp
+
+
+def gp_rollout(pack, h0, a, eps, var_add, *params, reverse=False):
+    """(traj (T, N, Do), entropy ()) of the recurrence above with a grad_fn into h0, a, var_add and the five parameter tensors."""
+    h0, a, eps, var_add = _rollout_args(pack, h0, a, eps, var_add)
+    return _GpRollout.apply(pack, bool(reverse), h0, a, eps.detach(), var_add, *_gp_args(pack, params))
+
+
+def gp_rollout_eval(pack, h0, a, eps, var_add, reverse=False):
+    """The forward launch alone on a pack that is already prepared: no saved variances, no grad_fn."""
+    h0, a, eps, var_add = _rollout_args(pack, h0, a, eps, var_add)
+    with torch.no_grad():
+        traj, _, ent = _rollout_forward(pack.layout, pack.buf, h0.contiguous(), a.contiguous() if a is not None else None,
+                                        eps.contiguous(), var_add.contiguous() if var_add is not None else None, reverse, False)
+    return traj, ent

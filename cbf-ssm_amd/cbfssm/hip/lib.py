@@ -30,6 +30,8 @@ SYMBOLS = (
     'cbfssm_input_adjoint_fwd_elems', 'cbfssm_input_adjoint_bwd_elems', 'cbfssm_input_adjoint_obs_elems',
     'cbfssm_forward_pass_bwd_in_f64', 'cbfssm_backward_pass_bwd_in_f64', 'cbfssm_input_grads_f64',
     'cbfssm_gp_predict_bwd_workgroups', 'cbfssm_gp_predict_bwd_work_elems', 'cbfssm_gp_predict_bwd_f64', 'cbfssm_gp_tail_f64',
+    'cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_f64', 'cbfssm_gp_rollout_bwd_workgroups', 'cbfssm_gp_rollout_bwd_work_elems',
+    'cbfssm_gp_rollout_bwd_f64',
 )
 
 
@@ -159,6 +161,13 @@ def load():
         getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]
     lib.cbfssm_gp_predict_bwd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     lib.cbfssm_gp_tail_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, dbl, vp, vp, vp, vp, vp]
+    for name in ('cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_bwd_workgroups'):
+        getattr(lib, name).restype = i64
+        getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]
+    lib.cbfssm_gp_rollout_bwd_work_elems.restype = i64
+    lib.cbfssm_gp_rollout_bwd_work_elems.argtypes = [C.POINTER(PackLayout), i64, i64]
+    lib.cbfssm_gp_rollout_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, vp, vp, i64, i64, ip, vp, vp, vp, vp]
+    lib.cbfssm_gp_rollout_bwd_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [i64, i64, ip] + [vp] * 6
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith('_elems'):                 # element counts: 64-bit results (set above)

@@ -14,7 +14,8 @@ GPModel is differentiable: when one of its five leaf tensors (`GPModel.parameter
 and `prior_kl` return tensors with a grad_fn (cbfssm.hip.autograd.gp_predict / gp_prior_kl: hand-written adjoint kernels,
 no tensor-library fallback), so a model built around a sparse GP -- the reference's Voliro pattern, gp_f.predict plus a
 physics term (cbfssm/model/voliro.py:106-123) -- trains with torch.optim.  Without a gradient request both are the
-evaluation-only calls they always were.
+evaluation-only calls they always were.  `GPModel.rollout` (not in the reference) runs the GP's recurrence over time with
+per-chain inputs as one fused launch, differentiable in the same way.
 """
 import ctypes as C
 import numpy as np
@@ -189,3 +190,21 @@ class GPModel:
             from ..hip import autograd as _ag
             return _ag.gp_prior_kl(self._pack, *self.parameters())
         return self._prepared().scal[_l.SCAL_KLZ].clone()                                                        # :163-172
+
+    def rollout(self, h0, a, eps, var_add=None, reverse=False):
+        """An addition to the reference's surface (its GPModel has predict and prior_kl only): the recurrence
+
+            for t in 0..T-1 (reverse: T-1..0):  fmean, fvar = predict(concat(h, a[t]));  v = fvar + var_add
+                                                h = h + fmean + eps[t][:, None] * sqrt(v);  traj[t] = h
+            entropy = 0.5 * sum(log(2 pi e v))
+
+        as one launch -- the loop of Voliro's recognition run (cbfssm/model/voliro.py:139-186: reverse=True, h0 = 0,
+        a = (u_t, y_t) per particle) and of a CBF-SSM's free-running transition (cbfssm/model/cbfssm.py:199-206,224).
+        h0 (N, out_dim), a (T, N, in_dim - out_dim) or None when the GP takes the state alone, eps (T, N) standard normals,
+        var_add (out_dim) constrained values or None.  Returns (traj (T, N, out_dim), entropy ()).  When a leaf, h0, a or
+        var_add requires grad both results carry a grad_fn (cbfssm.hip.autograd.gp_rollout; eps gets no gradient);
+        otherwise the forward kernel runs alone and keeps nothing for an adjoint."""
+        from ..hip import autograd as _ag
+        if self._wants_grad(h0, a, var_add):
+            return _ag.gp_rollout(self._pack, h0, a, eps, var_add, *self.parameters(), reverse=reverse)
+        return _ag.gp_rollout_eval(self._prepared(), h0, a, eps, var_add, reverse=reverse)

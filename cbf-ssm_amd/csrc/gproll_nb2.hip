@@ -1,0 +1,2 @@
+#include "cbfssm_gp_rollout.hpp"
+CBF_GPROLL_INSTANTIATE(2)

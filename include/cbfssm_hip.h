@@ -182,6 +182,49 @@ int cbfssm_gp_tail_f64(const cbfssm_pack_layout* layout, const double* pack, con
                        void* stream);
 
 /*
+ * ---- differentiable GP rollout: the time loop of ONE sparse GP with per-chain inputs, and its adjoint.
+ * Replaces the loop bodies of Voliro's recognition run (cbfssm/model/voliro.py:139-186: one run from h = 0, backwards in
+ * time, GP input (h, u_t, y_t) with a per-particle u_t) and of the free-running transition of a trained CBF-SSM
+ * (cbfssm/model/cbfssm.py:199-206,224), which the pass kernels above cannot run: their u / y are shared by the particles.
+ *
+ *   for t = 0 .. T-1 (reverse != 0: T-1 .. 0):
+ *       fmean, fvar = GPModel.predict(concat(h, a[t]))               gp_tf.py:132-161
+ *       v = fvar + var_add                                           (var_add NULL: v = fvar)
+ *       h = h + fmean + eps[t] sqrt(v);  traj[t] = h                 one normal per chain and step (cbfssm.py:149,209)
+ *       entropy += 0.5 sum log(2 pi e v)                             cbfssm.py:154-155, voliro.py:182-183
+ *
+ * cbfssm_gp_rollout_f64 (voliro.py:139-186, cbfssm.py:199-206,224): h0 (N, Do), a (T, N, Da) with Da = D - Do (NULL when
+ * Da = 0), eps (T, N), var_add (Do) constrained values or NULL -> traj (T, N, Do), every entry written once; vsave
+ * (T, N, Do) or NULL: v of every step, kept for the adjoint; ent_part: cbfssm_gp_rollout_partials doubles, one partial
+ * per 16 chains, whose sum is `entropy`.  One launch, one workgroup per 16 chains, both GP forms (layout->gp_form).
+ *
+ * cbfssm_gp_rollout_bwd_f64 (voliro.py:139-186, cbfssm.py:199-206,224 differentiated): pack, h0, a, eps, traj, vsave as in / from the forward call,
+ * gtraj (T, N, Do) = d loss / d traj, g_ent: ONE double on the device = d loss / d entropy
+ *   -> gh0 (N, Do), ga (T, N, Da; NULL when Da = 0): every entry written once;
+ *      gpart: cbfssm_gp_rollout_bwd_workgroups slabs of layout->rev_slab doubles ("Slab layout of the parameter adjoints
+ *      of one GP" below) with room for CBFSSM_REDUCE_SPLIT more; the d/d var_x entries hold d loss / d var_add by state
+ *      dim; cbfssm_reduce_partials_f64 and cbfssm_gp_tail_f64 (kl_weight 0) take them as they are;
+ *      M > 112 (layout->rev_stash): work (cbfssm_gp_rollout_bwd_work_elems doubles: the two operand images per
+ *      (workgroup, step) slot and the contraction's scratch) and gB_image ([NBLK][NBLK][4][64], cleared by the call) as in
+ *      cbfssm_gp_predict_bwd_f64; otherwise both may be NULL.
+ * The adjoint recomputes the kernel tile and A2 = K^-1 k of every step (K^-1 contraction, whatever the form of the
+ * forward).  No atomics, no host synchronisation; two calls are bitwise identical.  eps has no adjoint.
+ * The three counts are host arithmetic: -1 for a bad layout or a negative size.  The calls: NULL pointers and T < 1 -> -1;
+ * beyond the limits of cbfssm_gp_predict_f64 (M <= 320, Do <= D <= 24, Do <= 16) or N > 2^30, T > 2^24 -> -3, before
+ * any launch.
+ */
+int64_t cbfssm_gp_rollout_partials(const cbfssm_pack_layout* layout, int64_t N);
+int cbfssm_gp_rollout_f64(const cbfssm_pack_layout* layout, const double* pack, const double* h0, const double* a,
+                          const double* eps, const double* var_add, int64_t N, int64_t T, int reverse, double* traj,
+                          double* vsave, double* ent_part, void* stream);
+int64_t cbfssm_gp_rollout_bwd_workgroups(const cbfssm_pack_layout* layout, int64_t N);
+int64_t cbfssm_gp_rollout_bwd_work_elems(const cbfssm_pack_layout* layout, int64_t N, int64_t T);
+int cbfssm_gp_rollout_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* h0, const double* a,
+                              const double* eps, const double* traj, const double* vsave, const double* gtraj,
+                              const double* g_ent, int64_t N, int64_t T, int reverse, double* gh0, double* ga,
+                              double* gpart, double* work, double* gB_image, void* stream);
+
+/*
  * Both backward (recognition) runs, CBFSSM._backward/_backward_run/_backward_body (cbfssm.py:84-158).
  *   u (B,T,dim_u), y (B,T,dim_y), hid_b (2,T,N), eps_b (2,T,N), var_x (dim_x)
  *   -> y2 (T,N,dim_x-dim_y)  [every t written by exactly one run, cbfssm.py:123-128,151]
