@@ -13,7 +13,8 @@ import torch
 PARAMS = ('zeta_pos', 'zeta_mean', 'zeta_var_unc', 'variance_unc', 'lengthscales_unc')
 KL_WEIGHT = 0.3
 
-# (M, D, Do, npts): one case per compiled tile height plus the edges
+# (M, D, Do, npts): the shapes of the feature's own tests; tests/gp_tile_grid.py holds the table that reaches every compiled
+# (tile height, input width) leaf of the adjoint kernels
 CASES = [
     (12, 4, 3, 41),             # one row block, ragged columns
     (30, 7, 5, 16),

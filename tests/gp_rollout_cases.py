@@ -27,7 +27,8 @@ from gp_autograd_cases import PARAMS, within_rule   # noqa: F401  (re-exported)
 ENT_WEIGHT = 0.7
 LOG2PIE = float(np.log(2.0 * np.pi * np.e))
 
-# (M, D, Do, N, T, reverse, var_add): one case per compiled tile height plus the edges
+# (M, D, Do, N, T, reverse, var_add): the shapes of the feature's own tests; tests/gp_tile_grid.py holds the table that
+# reaches every compiled (tile height, input width, trim) leaf of the rollout kernels
 CASES = [
     (12, 4, 3, 21, 6, True, False),        # one row block, ragged columns
     (20, 19, 6, 37, 8, True, False),       # Voliro's recognition shape
