@@ -1,5 +1,6 @@
 """Differentiable torch functions over the HIP library: the CBF-SSM loss of a whole engine (`elbo_loss`), the two
-functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down) and its recurrence over time (`gp_rollout`, at the end).
+functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down), its recurrence over time (`gp_rollout`) and the
+rigid-body filter loop of the Voliro model (`rigid_filter`, at the end).
 
 The CBF-SSM loss:
 
@@ -327,3 +328,102 @@ def gp_rollout_eval(pack, h0, a, eps, var_add, reverse=False):
         traj, _, ent = _rollout_forward(pack.layout, pack.buf, h0.contiguous(), a.contiguous() if a is not None else None,
                                         eps.contiguous(), var_add.contiguous() if var_add is not None else None, reverse, False)
     return traj, ent
+
+
+# ---- Voliro's forward filter run: rigid-body step, Gaussian filter update, one sample and a KL term per step -------------
+#
+#     traj, kl = rigid_filter(body, x0, u, y, eps, var_x, var_y)
+#
+# body: a cbfssm.hip.lib.RigidBody (lib.rigid_body(mass_inv, inertia_inv, gravity, dt): host constants); x0 (N, 13),
+# u (S, N, 6), y (S, N, 13), eps (S, N) standard normals, var_x / var_y (13) CONSTRAINED values; traj (S, N, 13) time-major,
+# kl a 0-d tensor: the loop of cbfssm/model/voliro.py:188-242,314-338 (state: pos 0:3, quaternion 3:7 scalar first,
+# linvel 7:10, angvel 10:13).  Forward: cbfssm_rigid_filter_f64, the KL partials summed in a fixed order by
+# cbfssm_reduce_partials_f64.  Backward: cbfssm_rigid_filter_bwd_f64 (recomputes every step from the trajectory) ->
+# cbfssm_reduce_partials_f64; gradients for x0, u, y, var_x, var_y, none for eps.  Once differentiable, no host
+# synchronisation.  There is no tensor-library form of this loop in the package.
+
+def _rigid_forward(body, x0, u, y, eps, var_x, var_y):
+    lib = _l.load()
+    S, N = eps.shape
+    dev = x0.device
+    if S < 1:
+        raise ValueError('rigid_filter: at least one time step')
+    traj = torch.empty(S, N, 13, dtype=torch.float64, device=dev)
+    if N == 0:
+        return traj, torch.zeros((), dtype=torch.float64, device=dev)
+    npart = int(lib.cbfssm_rigid_filter_partials(N))
+    if npart < 1:
+        raise _l.CbfssmHipError('cbfssm_rigid_filter_partials refused N = %d' % N)
+    kl_part = torch.empty(npart + 32, dtype=torch.float64, device=dev)                      # (+ CBFSSM_REDUCE_SPLIT)
+    _l.check(lib.cbfssm_rigid_filter_f64(C.byref(body), _ptr(x0), _ptr(u), _ptr(y), _ptr(eps), _ptr(var_x), _ptr(var_y), N, S,
+                                         _ptr(traj), _ptr(kl_part), _stream()), 'cbfssm_rigid_filter_f64')
+    kl = torch.empty(1, dtype=torch.float64, device=dev)
+    _l.check(lib.cbfssm_reduce_partials_f64(_ptr(kl_part), 1, npart, _ptr(kl), _stream()), 'cbfssm_reduce_partials_f64')
+    return traj, kl.reshape(())
+
+
+def _rigid_args(body, x0, u, y, eps, var_x, var_y):
+    if not isinstance(body, _l.RigidBody):
+        raise TypeError('rigid_filter: body must be a cbfssm.hip.lib.RigidBody (lib.rigid_body(...))')
+    if not (torch.is_tensor(x0) and x0.is_cuda):
+        raise ValueError('rigid_filter: x0 must be a device tensor')
+    dev = x0.device
+    x0, u, y, eps, var_x, var_y = (torch.as_tensor(t, dtype=torch.float64, device=dev) for t in (x0, u, y, eps, var_x, var_y))
+    assert eps.dim() == 2, 'eps (S, N)'
+    S, N = eps.shape
+    assert tuple(x0.shape) == (N, 13) and tuple(u.shape) == (S, N, 6) and tuple(y.shape) == (S, N, 13), \
+        'x0 (N, 13), u (S, N, 6), y (S, N, 13)'
+    assert tuple(var_x.shape) == (13,) and tuple(var_y.shape) == (13,), 'var_x, var_y (13)'
+    return x0, u, y, eps, var_x, var_y
+
+
+class _RigidFilter(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, body, x0, u, y, eps, var_x, var_y):
+        saved = tuple(t.detach().contiguous() for t in (x0, u, y, eps, var_x, var_y))
+        traj, kl = _rigid_forward(body, *saved)
+        ctx.body = body
+        ctx.save_for_backward(*saved, traj)                                                  # (traj is an output)
+        return traj, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gtraj, gkl):
+        lib = _l.load()
+        x0, u, y, eps, var_x, var_y, traj = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        S, N = eps.shape
+        dev = eps.device
+        gx0, gu, gy = torch.empty_like(x0), torch.empty_like(u), torch.empty_like(y)
+        gvx = gvy = None
+        if N == 0:
+            if need[5] or need[6]:
+                gvx, gvy = torch.zeros_like(var_x), torch.zeros_like(var_y)
+        else:
+            gtraj = gtraj.contiguous()
+            gkl = gkl.reshape(1).contiguous()
+            nwg = int(lib.cbfssm_rigid_filter_partials(N))
+            gpart = torch.empty((nwg + 32) * 32, dtype=torch.float64, device=dev)          # (+ CBFSSM_REDUCE_SPLIT)
+            _l.check(lib.cbfssm_rigid_filter_bwd_f64(C.byref(ctx.body), _ptr(x0), _ptr(u), _ptr(y), _ptr(eps), _ptr(var_x),
+                                                     _ptr(var_y), _ptr(traj), _ptr(gtraj), _ptr(gkl), N, S, _ptr(gx0),
+                                                     _ptr(gu), _ptr(gy), _ptr(gpart), _stream()), 'cbfssm_rigid_filter_bwd_f64')
+            if need[5] or need[6]:
+                red = torch.empty(32, dtype=torch.float64, device=dev)
+                _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), 32, nwg, _ptr(red), _stream()), 'cbfssm_reduce_partials_f64')
+                gvx, gvy = red[0:13].clone(), red[13:26].clone()
+        return (None, gx0 if need[1] else None, gu if need[2] else None, gy if need[3] else None, None,
+                gvx if need[5] else None, gvy if need[6] else None)
+
+
+def rigid_filter(body, x0, u, y, eps, var_x, var_y):
+    """(traj (S, N, 13), kl ()) of the loop above with a grad_fn into x0, u, y, var_x and var_y."""
+    x0, u, y, eps, var_x, var_y = _rigid_args(body, x0, u, y, eps, var_x, var_y)
+    return _RigidFilter.apply(body, x0, u, y, eps.detach(), var_x, var_y)
+
+
+def rigid_filter_eval(body, x0, u, y, eps, var_x, var_y):
+    """The forward launch alone: no grad_fn, nothing kept."""
+    args = _rigid_args(body, x0, u, y, eps, var_x, var_y)
+    with torch.no_grad():
+        return _rigid_forward(body, *(t.contiguous() for t in args))

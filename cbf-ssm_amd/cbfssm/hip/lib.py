@@ -32,6 +32,7 @@ SYMBOLS = (
     'cbfssm_gp_predict_bwd_workgroups', 'cbfssm_gp_predict_bwd_work_elems', 'cbfssm_gp_predict_bwd_f64', 'cbfssm_gp_tail_f64',
     'cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_f64', 'cbfssm_gp_rollout_bwd_workgroups', 'cbfssm_gp_rollout_bwd_work_elems',
     'cbfssm_gp_rollout_bwd_f64',
+    'cbfssm_rigid_filter_partials', 'cbfssm_rigid_filter_f64', 'cbfssm_rigid_filter_bwd_f64',
 )
 
 
@@ -49,6 +50,11 @@ class PackLayout(C.Structure):
 class Problem(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('B', 'S', 'T', 'dim_x', 'dim_u', 'dim_y', 'M', 'recog_len', 'condition',
                                           'half', 'group0', 'ngroups')] + [('k_factor', C.c_double)]
+
+
+class RigidBody(C.Structure):
+    """cbfssm_rigid_body: the host constants of Voliro's rigid-body step (cbfssm/model/voliro.py:39-45)"""
+    _fields_ = [('mass_inv', C.c_double), ('inertia_inv', C.c_double * 3), ('gravity', C.c_double * 3), ('dt', C.c_double)]
 
 
 class CbfssmHipError(RuntimeError):
@@ -168,6 +174,10 @@ def load():
     lib.cbfssm_gp_rollout_bwd_work_elems.argtypes = [C.POINTER(PackLayout), i64, i64]
     lib.cbfssm_gp_rollout_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, vp, vp, i64, i64, ip, vp, vp, vp, vp]
     lib.cbfssm_gp_rollout_bwd_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [i64, i64, ip] + [vp] * 6
+    lib.cbfssm_rigid_filter_partials.restype = i64
+    lib.cbfssm_rigid_filter_partials.argtypes = [i64]
+    lib.cbfssm_rigid_filter_f64.argtypes = [C.POINTER(RigidBody)] + [vp] * 6 + [i64, i64] + [vp] * 3
+    lib.cbfssm_rigid_filter_bwd_f64.argtypes = [C.POINTER(RigidBody)] + [vp] * 9 + [i64, i64] + [vp] * 5
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith('_elems'):                 # element counts: 64-bit results (set above)
@@ -190,6 +200,14 @@ def check(rc, what):
     if rc != 0:
         msg = load().cbfssm_last_error().decode('utf-8', 'replace')
         raise CbfssmHipError('%s failed (rc=%d): %s' % (what, rc, msg))
+
+
+def rigid_body(mass_inv, inertia_inv, gravity, dt):
+    rb = RigidBody()
+    rb.mass_inv, rb.dt = float(mass_inv), float(dt)
+    rb.inertia_inv[:] = [float(v) for v in inertia_inv]
+    rb.gravity[:] = [float(v) for v in gravity]
+    return rb
 
 
 def pack_layout(M, D, Do):

@@ -225,6 +225,56 @@ int cbfssm_gp_rollout_bwd_f64(const cbfssm_pack_layout* layout, const double* pa
                               double* gpart, double* work, double* gB_image, void* stream);
 
 /*
+ * ---- Voliro's forward filter run: the rigid-body time loop and its adjoint.
+ * Replaces _forward / _forward_body / symplectic_euler of the reference's fourth model (cbfssm/model/voliro.py:188-242,
+ * 314-338 with cbfssm/utils/quaternions.py), for S = T - 1 steps and N = B * samples chains:
+ *
+ *   q = var_x (13), r = var_y (13) constrained values,  k = q / (q + r),  sig = (1-k)^2 q + k^2 r        (loop invariant)
+ *   x = x0
+ *   for t = 0 .. S-1:
+ *       f   = symplectic_euler(x, u[t])       rot_vec(u[:3], rot), rot_vec(inertia_inv * u[3:], rot), linvel += (mass_inv
+ *                                             f_glob + gravity) dt, angvel += t_glob dt, pos += linvel dt,
+ *                                             rot += 0.5 (0, angvel) (x) rot dt, rot /= |rot|
+ *       mu  = f + k (y[t] - f)
+ *       x   = mu + eps[t] sqrt(sig);  traj[t] = x                     one normal per chain and step (voliro.py:233)
+ *       kl += 0.5 sum_d (log q - log sig + (sig + (mu - f)^2) / q - 1)                              voliro.py:238-239
+ *
+ * State layout: pos 0:3, quaternion 3:7 (scalar first, the product of quaternions.py:8-13), linvel 7:10, angvel 10:13.
+ * The physical constants are host values in a cbfssm_rigid_body, passed by pointer and read before the call returns.
+ *
+ * cbfssm_rigid_filter_f64 (voliro.py:188-242,314-338): x0 (N, 13), u (S, N, 6), y (S, N, 13), eps (S, N), var_x, var_y (13)
+ *   -> traj (S, N, 13), every entry written exactly once; kl_part: cbfssm_rigid_filter_partials(N) doubles, one partial
+ *      per workgroup of 64 chains, with room for CBFSSM_REDUCE_SPLIT more: cbfssm_reduce_partials_f64(kl_part, 1, n, out)
+ *      sums them to `kl`.  One launch, one lane per chain.
+ *
+ * cbfssm_rigid_filter_bwd_f64 (voliro.py:188-242,314-338 differentiated): body, x0, u, y, eps, var_x, var_y as in, traj from,
+ * the forward call; gtraj (S, N, 13) = d loss / d traj; g_kl: ONE double on the device = d loss / d kl
+ *   -> gx0 (N, 13), gu (S, N, 6), gy (S, N, 13): every entry written once, no read of their prior content;
+ *      gpart: cbfssm_rigid_filter_partials(N) slabs of 32 doubles [d/d var_x (13) | d/d var_y (13) | padding], with room
+ *      for CBFSSM_REDUCE_SPLIT more; cbfssm_reduce_partials_f64(gpart, 32, n, out) sums them.  The 26 numbers include the
+ *      data-independent part of the KL (N S g_kl d/d(q, r) of 0.5 sum (log q - log sig + sig / q - 1)) and the
+ *      eps d sqrt(sig) path.
+ * The reverse sweep recomputes every step's f from traj[t-1] (x0 at t = 0) and u[t]: nothing is saved except the
+ * trajectory.  No atomics, no allocation, no synchronisation; two calls are bitwise identical.  eps has no adjoint.
+ * cbfssm_rigid_filter_partials is host arithmetic: ceil(N / 64), -1 for N < 0 (or N > 2^30).  The calls: NULL pointers,
+ * N < 0 or S < 1 -> -1; N > 2^30 or S > 2^24 -> -3; both decided on the host before any launch.  N = 0 launches nothing.
+ */
+typedef struct cbfssm_rigid_body {
+    double mass_inv;
+    double inertia_inv[3];
+    double gravity[3];
+    double dt;
+} cbfssm_rigid_body;
+int64_t cbfssm_rigid_filter_partials(int64_t N);
+int cbfssm_rigid_filter_f64(const cbfssm_rigid_body* body, const double* x0, const double* u, const double* y,
+                            const double* eps, const double* var_x, const double* var_y, int64_t N, int64_t S,
+                            double* traj, double* kl_part, void* stream);
+int cbfssm_rigid_filter_bwd_f64(const cbfssm_rigid_body* body, const double* x0, const double* u, const double* y,
+                                const double* eps, const double* var_x, const double* var_y, const double* traj,
+                                const double* gtraj, const double* g_kl, int64_t N, int64_t S, double* gx0, double* gu,
+                                double* gy, double* gpart, void* stream);
+
+/*
  * Both backward (recognition) runs, CBFSSM._backward/_backward_run/_backward_body (cbfssm.py:84-158).
  *   u (B,T,dim_u), y (B,T,dim_y), hid_b (2,T,N), eps_b (2,T,N), var_x (dim_x)
  *   -> y2 (T,N,dim_x-dim_y)  [every t written by exactly one run, cbfssm.py:123-128,151]
