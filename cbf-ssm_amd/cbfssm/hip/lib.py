@@ -18,7 +18,7 @@ SYMBOLS = (
     'cbfssm_last_error', 'cbfssm_version', 'cbfssm_gp_pack_layout', 'cbfssm_kmm_chol_f64', 'cbfssm_gp_prepare_f64',
     'cbfssm_gp_predict_f64', 'cbfssm_backward_pass_partials', 'cbfssm_backward_pass_f64',
     'cbfssm_forward_pass_partials', 'cbfssm_forward_pass_f64', 'cbfssm_loglik_moments_f64',
-    'cbfssm_elbo_combine_f64', 'cbfssm_rev_workgroups', 'cbfssm_forward_pass_bwd_f64',
+    'cbfssm_elbo_combine_f64', 'cbfssm_rev_workgroups', 'cbfssm_bwd_schedule', 'cbfssm_forward_pass_bwd_f64',
     'cbfssm_backward_pass_bwd_f64', 'cbfssm_reduce_partials_f64', 'cbfssm_gp_prepare2_f64', 'cbfssm_bwd_segments', 'cbfssm_forward_pass_bwd_ex_f64',
     'cbfssm_backward_pass_bwd_ex_f64', 'cbfssm_half_forward_pass_f64', 'cbfssm_half_forward_pass_bwd_f64',
     'cbfssm_saved_a2_elems', 'cbfssm_param_layout_init', 'cbfssm_constrain_f64', 'cbfssm_train_tail_work_elems',
@@ -126,6 +126,8 @@ def load():
     lib.cbfssm_elbo_combine_f64.argtypes = [C.POINTER(Problem), dbl, dbl, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.cbfssm_rev_workgroups.restype = i64
     lib.cbfssm_rev_workgroups.argtypes = [C.POINTER(Problem), ip]
+    lib.cbfssm_bwd_schedule.restype = ip
+    lib.cbfssm_bwd_schedule.argtypes = [C.POINTER(Problem), ip] + [C.POINTER(C.c_int)] * 3
     lib.cbfssm_forward_pass_bwd_f64.argtypes = [C.POINTER(Problem), C.POINTER(PackLayout)] + [vp] * 10 + [dbl, vp, vp, vp]
     lib.cbfssm_backward_pass_bwd_f64.argtypes = [C.POINTER(Problem), C.POINTER(PackLayout)] + [vp] * 10 + [dbl, vp, vp]
     lib.cbfssm_bwd_segments.argtypes = [C.POINTER(Problem)]

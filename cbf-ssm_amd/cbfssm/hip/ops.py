@@ -416,9 +416,8 @@ class TimeLoops:
         lib, ws = _l.load(), self.ws
         a = self._bwd_args(q) + (_ptr(ws.h_all), _ptr(ws.fmv_b), _ptr(ws.a2s_b), _ptr(ws.gy2), self.cE, _ptr(ws.gpart_b))
         if self.in_bufs is not None:
-            if chunk is None:       # the whole sweep, chunked over grid.z as cbfssm_backward_pass_bwd_f64 does
-                groups = (q.B * q.S + 15) // 16
-                nchunk = int(lib.cbfssm_rev_workgroups(C.byref(q), 1)) // (2 * groups)
+            if chunk is None:       # the whole sweep by the library's chunk table, as cbfssm_backward_pass_bwd_f64 runs it
+                nchunk = 0
                 chunk = (0, int(lib.cbfssm_bwd_segments(C.byref(q))), None, None, 0)
             else:
                 nchunk = 1

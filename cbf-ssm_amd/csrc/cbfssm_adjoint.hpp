@@ -29,6 +29,16 @@ struct RevPackPtrs {
     const double* ZT;    // [NBLK][JB][4][64]  A[row j][k = m], row D is all ones (for m < M)
 };
 
+// Backward-run adjoint: the chunk table of one launch.  Entry e (grid.y, in launch order) is nsteps[e] consecutive steps
+// from t_begin[e] upwards of run[e]: whole resample-to-resample segments, so every entry is an independent workgroup set
+// with its own slab.  Filled on the host (cbfssm_bwd_schedule, or the explicit segment ranges of stash mode).
+constexpr int BWD_SCHED_CAP = 32;
+struct BwdSched {
+    int run[BWD_SCHED_CAP];
+    int t_begin[BWD_SCHED_CAP];
+    int nsteps[BWD_SCHED_CAP];
+};
+
 struct RevArgs {
     PackPtrs pk;
     RevPackPtrs rk;
@@ -54,8 +64,7 @@ struct RevArgs {
     int KSr;               // ceil(M / 4)
     // time range of this launch
     int t_hi, t_lo;        // fwd: steps t = t_hi .. t_lo (descending), t_hi <= T-2
-    int seg0, seg1;        // bwd: resample-to-resample segments [seg0, seg1) of each run, split over grid.z chunks
-    int nchunk;            // bwd: grid.z
+    BwdSched sched;        // bwd: the chunk of every grid.y index
     double* gx_carry;      // fwd: (N, dim_x) adjoint of x_{t_lo} handed to the next launch (null: single launch)
     // stash mode (tile heights whose K^-1-adjoint does not fit the VGPR file): the A2bar^T and K^T operand images of
     // every step go to HBM, [slot = workgroup * chunk_steps + step][NBLK][4][64] doubles each (stash_ld = 16 x slots);
@@ -262,10 +271,10 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
     const int c = min(c0 + nl, N - 1);
     const bool cvalid = (c0 + nl) < N;
     const int bq = c / S;
-    const int run = (MODE == MODE_BWD) ? int(blockIdx.y) : 0;
+    const int run = (MODE == MODE_BWD) ? a.sched.run[blockIdx.y] : 0;
     const int R = a.recog_len, P = 2 * R;
     const int KSr = a.KSr;                              // k-steps of K^-1 that carry data: ceil(M/4)
-    const int64_t wg_linear = (int64_t(blockIdx.z) * gridDim.y + blockIdx.y) * a.gtotal + gx;
+    const int64_t wg_linear = int64_t(blockIdx.y) * a.gtotal + gx;
 
     // ---- loop-invariant operands (Z~ rows and cz of the owned row blocks stay in VGPRs; the small operand images
     // muA/s2A/muB/s2B/ZT are re-read from L1/L2 where they are used: the VGPRs hold the adjoint accumulators)
@@ -344,21 +353,15 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB + (rev_extra_wave(NBLK, 
     for (int i = 0; i < RB; ++i) bop[i] = BLDS ? (Bl + rbs[i] * KSr * 64 + l) : (a.pk.Bp + rbs[i] * KS * 64 + l);
     __syncthreads();
 
-    // ---- time range.  Backward runs: chunk z of run y covers whole resample-to-resample segments (the carried
-    // adjoint is zero at a segment start, cbfssm.py:133-136), so chunks are independent workgroups.
+    // ---- time range.  Backward runs: a chunk covers whole resample-to-resample segments (the carried adjoint is zero
+    // at a segment start, cbfssm.py:133-136), so chunks are independent workgroups.
     int t_begin = 0, nsteps = 0;
     if (MODE == MODE_FWD) {
         nsteps = a.t_hi - a.t_lo + 1;
         if (nsteps < 0) nsteps = 0;
     } else {
-        const int o = run * R;
-        const int z = blockIdx.z, nz = a.nchunk;
-        const int nsg = a.seg1 - a.seg0;
-        const int k0 = a.seg0 + (z * nsg) / nz, k1 = a.seg0 + ((z + 1) * nsg) / nz;   // segment k starts at max(0, P*k - o)
-        const int tb = (k0 <= 0) ? 0 : min(T, P * k0 - o);
-        const int te = min(T, max(0, P * k1 - o));
-        t_begin = tb;
-        nsteps = max(0, te - tb);
+        t_begin = a.sched.t_begin[blockIdx.y];
+        nsteps = a.sched.nsteps[blockIdx.y];
     }
     if (MODE == MODE_FWD && nsteps > 0) {
 #pragma unroll

@@ -6,6 +6,10 @@
 #include <cstring>
 #include <cstdarg>
 #include <cstdlib>
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <vector>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_inst.hpp"
 #include "cbfssm_adjoint_inst.hpp"
@@ -1303,17 +1307,84 @@ int cbfssm_elbo_combine_f64(const cbfssm_problem* p, double lambda0, double lamb
     return check_launch("elbo_combine");
 }
 
-static int rev_chunks(const cbfssm_problem* p)
+// ---- the backward-run schedule.  A function of (T, recog_len, B*S) only: never of a launch's chain-group range, so that
+// the chain-group split reproduces the single launch bitwise.
+//
+// Live steps: run 0 is all of t = 0 .. T-1 in segments that start at 0, 2R, 4R, ...; run 1 starts at t = R (its first
+// segment t = R-1 .. 0 writes nothing to y2, adds nothing to the entropy and its final h is dropped: cbfssm.py:112,
+// 123-128,151,156), in segments that start at R, 3R, 5R, ...  Only the last segment of a run can be shorter than 2R.
+//
+// Chunks: the segments of a run in time order are cut into runs of c = min(m, max(1, remaining / 2)) whole segments: a
+// head of m-segment chunks that halves down to a tail of single segments (the run's short last segment among them).
+// Both runs' chunks are then listed longest first.  m is the value whose table a greedy list schedule on the chip's
+// workgroup slots finishes first (one adjoint workgroup per CU, every workgroup its steps plus a prologue of about two
+// steps); ties go to the larger m, which has fewer chunks (a chunk is one slab and one K^-1-to-LDS prologue).
+constexpr int SCHED_UNITS = 256;         // CUs of the MI355X: the adjoint runs one workgroup per CU
+constexpr int SCHED_PER_RUN = 16;        // chunks per run and chain group at most
+constexpr int SCHED_PROLOGUE = 2;        // a workgroup's prologue and slab write, in steps (the model's only constant)
+
+struct SchedEntry { int run, t_begin, nsteps; };
+
+static bool sched_table(int T, int R, int m, std::vector<SchedEntry>& out)
 {
-    // enough workgroups for ~5 rounds over 256 CUs (one adjoint workgroup per CU), never more chunks than segments
-    const int64_t groups = (int64_t(p->B) * p->S + 15) / 16;
-    const int P = 2 * p->recog_len;
-    const int nseg = p->T / P + 1;
-    int64_t c = (1280 + 2 * groups - 1) / (2 * groups);
-    if (c > nseg) c = nseg;
-    if (c < 1) c = 1;
-    if (c > 64) c = 64;
-    return int(c);
+    const int P = 2 * R;
+    out.clear();
+    for (int run = 0; run < 2; ++run) {
+        const int start = run * R;
+        int rem = (T > start) ? (T - start + P - 1) / P : 0, pos = 0, cnt = 0;
+        while (rem > 0) {
+            const int c = std::min(m, std::max(1, rem / 2));
+            const int tb = start + P * pos, te = std::min(T, start + P * (pos + c));
+            out.push_back({run, tb, te - tb});
+            pos += c; rem -= c;
+            if (++cnt > SCHED_PER_RUN) return false;
+        }
+    }
+    std::stable_sort(out.begin(), out.end(), [](const SchedEntry& x, const SchedEntry& y) { return x.nsteps > y.nsteps; });
+    return true;
+}
+
+// makespan of the table under greedy list scheduling: `groups` equal workgroups per entry, in table order, each to the
+// slot that frees first.  Slots are kept as (free time -> count), so an entry costs a few map operations.
+static int64_t sched_makespan(const std::vector<SchedEntry>& tab, int64_t groups)
+{
+    std::map<int64_t, int64_t> slots;
+    slots[0] = SCHED_UNITS;
+    for (const SchedEntry& e : tab) {
+        int64_t left = groups;
+        while (left > 0) {
+            auto it = slots.begin();
+            const int64_t t = it->first, take = std::min(left, it->second);
+            if ((it->second -= take) == 0) slots.erase(it);
+            slots[t + e.nsteps + SCHED_PROLOGUE] += take;
+            left -= take;
+        }
+    }
+    return slots.rbegin()->first;
+}
+
+static void bwd_schedule(int T, int R, int64_t n, std::vector<SchedEntry>& best)
+{
+    // (one shape per training run: the last result is kept)
+    static std::mutex mu;
+    static int cT = -1, cR = -1;
+    static int64_t cn = -1;
+    static std::vector<SchedEntry> cached;
+    std::lock_guard<std::mutex> lock(mu);
+    if (T != cT || R != cR || n != cn) {
+        const int64_t groups = (n + 15) / 16;
+        const int P = 2 * R;
+        std::vector<SchedEntry> tab;
+        int64_t best_t = -1;
+        cached.clear();
+        for (int m = std::max(1, (T + P - 1) / P); m >= 1; --m) {
+            if (!sched_table(T, R, m, tab)) break;             // smaller m: more chunks still
+            const int64_t t = sched_makespan(tab, groups);
+            if (best_t < 0 || t < best_t) { best_t = t; cached = tab; }
+        }
+        cT = T; cR = R; cn = n;
+    }
+    best = cached;
 }
 
 static int bwd_total_segments(const cbfssm_problem* p)
@@ -1322,10 +1393,26 @@ static int bwd_total_segments(const cbfssm_problem* p)
     return (p->T - 1 + p->recog_len) / (2 * p->recog_len) + 1;
 }
 
+int cbfssm_bwd_schedule(const cbfssm_problem* p, int cap, int* run, int* t_begin, int* nsteps)
+{
+    if (!p || p->recog_len < 1 || p->T < 1 || p->B < 1 || p->S < 1) return fail(-1, "bad problem");
+    std::vector<SchedEntry> tab;
+    bwd_schedule(p->T, p->recog_len, int64_t(p->B) * p->S, tab);
+    const int n = int(tab.size());
+    if (run || t_begin || nsteps) {
+        if (!run || !t_begin || !nsteps || cap < n) return fail(-1, "schedule has %d entries (cap %d)", n, cap);
+        for (int i = 0; i < n; ++i) { run[i] = tab[i].run; t_begin[i] = tab[i].t_begin; nsteps[i] = tab[i].nsteps; }
+    }
+    return n;
+}
+
 int64_t cbfssm_rev_workgroups(const cbfssm_problem* p, int backward_runs)
 {
     if (!p || p->recog_len < 1) return -1;
-    return (int64_t(p->B) * p->S + 15) / 16 * (backward_runs ? 2 * rev_chunks(p) : 1);
+    const int64_t groups = (int64_t(p->B) * p->S + 15) / 16;
+    if (!backward_runs) return groups;
+    const int n = cbfssm_bwd_schedule(p, 0, nullptr, nullptr, nullptr);
+    return n < 0 ? -1 : groups * n;
 }
 
 int cbfssm_bwd_segments(const cbfssm_problem* p)
@@ -1459,8 +1546,12 @@ static int backward_pass_bwd_impl(const cbfssm_problem* p, const cbfssm_pack_lay
     if (rc) return rc;
     if (!pack_b || !var_x || !u || !y || !hid_b || !eps_b || !h_all || !fmv_b || !gy2 || !gpart)
         return fail(-1, "null pointer");
-    if (seg0 < 0 || seg1 <= seg0 || seg1 > bwd_total_segments(p) || nchunk < 1 || nchunk > seg1 - seg0)
+    const bool whole = (nchunk == 0);                    // the library's own schedule of the whole sweep
+    if (whole ? (seg0 != 0 || seg1 != bwd_total_segments(p))
+              : (seg0 < 0 || seg1 <= seg0 || seg1 > bwd_total_segments(p) || nchunk < 1 || nchunk > seg1 - seg0 ||
+                 2 * nchunk > BWD_SCHED_CAP))
         return fail(-1, "bad segment range [%d, %d) / chunks %d", seg0, seg1, nchunk);
+    if (whole && L->rev_stash) return fail(-3, "M=%d runs in stash mode: explicit segment ranges only", L->M);
     RevArgs a;
     rc = fill_rev(a, p, L, pack_b, p->dim_x - p->dim_y);
     if (rc) return rc;
@@ -1474,16 +1565,43 @@ static int backward_pass_bwd_impl(const cbfssm_problem* p, const cbfssm_pack_lay
     a.fmv = fmv_b;
     a.a2s = a2s_b;
     a.ksave = a2s_b ? save_k(L) : 0;
-    a.seg0 = seg0; a.seg1 = seg1; a.nchunk = nchunk;
     const int64_t groups = (a.N + 15) / 16;
-    const int per = (seg1 - seg0 + nchunk - 1) / nchunk;
-    rc = set_stash(a, L, stash_a, stash_k, stash_ld, groups * 2 * nchunk, per * 2 * p->recog_len);
-    if (rc) return rc;
+    const int R = p->recog_len, P = 2 * R, T = p->T;
+    int nent;
+    if (whole) {
+        nent = cbfssm_bwd_schedule(p, BWD_SCHED_CAP, a.sched.run, a.sched.t_begin, a.sched.nsteps);
+        if (nent < 0) return nent;
+    } else {
+        // chunk z of run r is entry 2 z + r: segments [k0, k1) of the range, segment k of run r starting at max(0, P k - r R),
+        // less the dead steps t < R of run 1 (stash slots that fall out are zero-filled by the kernel's tail loop)
+        nent = 2 * nchunk;
+        const int nsg = seg1 - seg0;
+        for (int z = 0; z < nchunk; ++z)
+            for (int run = 0; run < 2; ++run) {
+                const int o = run * R;
+                const int k0 = seg0 + (z * nsg) / nchunk, k1 = seg0 + ((z + 1) * nsg) / nchunk;
+                const int tb = std::max(o, (k0 <= 0) ? 0 : std::min(T, P * k0 - o));
+                const int te = std::min(T, std::max(0, P * k1 - o));
+                a.sched.run[2 * z + run] = run;
+                a.sched.t_begin[2 * z + run] = std::min(tb, T);
+                a.sched.nsteps[2 * z + run] = std::max(0, te - tb);
+            }
+        const int per = (nsg + nchunk - 1) / nchunk;
+        rc = set_stash(a, L, stash_a, stash_k, stash_ld, groups * nent, per * P);
+        if (rc) return rc;
+    }
     int g0, ng, gt;
     rc = group_range(p, 1, &g0, &ng, &gt);
     if (rc) return rc;
     a.group0 = g0; a.gtotal = gt;
-    dim3 grid(unsigned(ng), 2, unsigned(nchunk));
+    if (input_grads && seg0 == 0 && a.gin && p->dim_u + p->dim_y > 0) {
+        // the dead rows t < R of run 1 have no owner: they read as zeros (every launch of a chain-group split writes the same)
+        const int64_t row = int64_t(p->dim_u + p->dim_y) * a.N;
+        if (hipMemsetAsync(a.gin + int64_t(T) * row, 0, sizeof(double) * std::min(R, T) * row, (hipStream_t)stream) != hipSuccess)
+            return fail(-2, "backward_pass_bwd: zeroing the dead input-adjoint rows failed");
+    }
+    if (nent == 0) return 0;
+    dim3 grid((unsigned)ng, (unsigned)nent);
     rc = input_grads ? dispatch_revin(L->NBLK, L->DK, MODE_BWD, a, grid, (hipStream_t)stream)
                      : dispatch_rev(L->NBLK, L->DK, MODE_BWD, a, grid, (hipStream_t)stream);
     if (rc) return fail(rc, "backward_pass_bwd launch failed (NBLK=%d DK=%d rc=%d)", L->NBLK, L->DK, rc);
@@ -1564,7 +1682,7 @@ int cbfssm_backward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_layo
     if (L && L->rev_stash) return fail(-3, "M=%d runs in stash mode: use cbfssm_backward_pass_bwd_ex_f64", L->M);
     if (!p || p->recog_len < 1) return fail(-1, "null problem");
     return cbfssm_backward_pass_bwd_ex_f64(p, L, pack_b, var_x, u, y, hid_b, eps_b, h_all, fmv_b, a2s_b, gy2, cE, gpart, 0,
-                                           bwd_total_segments(p), rev_chunks(p), nullptr, nullptr, 0, stream);
+                                           bwd_total_segments(p), 0, nullptr, nullptr, 0, stream);
 }
 
 int cbfssm_reduce_partials_f64(double* gpart, int64_t slab, int64_t nwg, double* out, void* stream)

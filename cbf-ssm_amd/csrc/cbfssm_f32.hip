@@ -358,20 +358,20 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void pass32_kernel(Arg
     const int c0 = gx * 16;
     const int G16 = (N + 15) >> 4;
 
-    int t_first, nsteps, dir, run = 0;
+    int t_first, nsteps, dir, run = 0, slot = 0;
     const int R = a.recog_len, P = 2 * R;
     if (MODE == MODE_FWD) {
         t_first = 0; nsteps = T - 1; dir = 1;
     } else {
         int k;
-        if (int(blockIdx.y) < a.nseg0) { run = 0; k = blockIdx.y + 1; }
-        else { run = 1; k = blockIdx.y - a.nseg0 + 1; }
+        bool dead;
+        slot = bwd_segment(blockIdx.y, a.nseg0, gridDim.y, run, k, dead);   // launch order and slots: cbfssm_kernels.hpp
         const int o = run * R;
         const int hi = min(P * k - 1 - o, T - 1);
         const int lo = (k > 1) ? (P * (k - 1) - o) : 0;
-        t_first = hi; nsteps = hi - lo + 1; dir = -1;
+        t_first = hi; nsteps = dead ? 0 : hi - lo + 1; dir = -1;
         if (nsteps <= 0) {
-            if (tid == 0) a.part_out[blockIdx.y * G16 + gx] = 0.0;
+            if (tid == 0) a.part_out[slot * G16 + gx] = 0.0;
             return;
         }
     }
@@ -555,7 +555,7 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void pass32_kernel(Arg
         }
     }
     const double tot = block_sum(v, red, tid, NT);
-    if (tid == 0) a.part_out[blockIdx.y * G16 + gx] = tot;
+    if (tid == 0) a.part_out[slot * G16 + gx] = tot;
 }
 
 template <int NBLK, int DK, bool TRI>

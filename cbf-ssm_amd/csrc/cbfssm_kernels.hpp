@@ -342,7 +342,7 @@ struct PassArgs {
     double* h_all;         // bwd, optional (2,T,N,Do)
     double* x_out;         // fwd: (T,N,dim_x)
     double* part_out;      // one partial per workgroup
-    int nseg0;             // bwd: number of segment slots of run 0 (blockIdx.y < nseg0 -> run 0)
+    int nseg0;             // bwd: number of segment slots of run 0 (grid.y -> run, segment, slot: bwd_segment below)
     double* dbg;           // diagnostic builds: [workgroup][32] stamp sums (null otherwise)
     int half;              // CBFSSMHALF forward pass (cbfssmhalf.py:117-172): x_0 from x0, Kalman update on d < dim_y only
     const double* x0;      // half: (B, dim_x) recognition-model output
@@ -355,6 +355,24 @@ struct PassArgs {
     int ksave;             // 1: the kernel tile K = k(Z, x_t) of every step is kept next to its A2 tile: a saved record is
                            // [A2: NBLK*256][K: NBLK*256] and the adjoint reads K instead of recomputing it (MFMA + exp)
 };
+
+// Backward runs: grid.y index -> (run, segment k) and the slot of the segment's entropy partial.  Segment k >= 1 of run r
+// is t = min(2R k - 1 - r R, T-1) .. max(0, 2R (k-1) - r R), walked downwards.  The slots keep the order run 0 k = 1 .. n0,
+// run 1 k = 1 .. n1 whatever the launch order, which puts the segments that are not whole last: first every run's whole
+// segments, then the top segment of run 0 and of run 1 (the only ones that can be short), then the dead first segment
+// of run 1 (t = R-1 .. 0: it writes nothing to y2, adds nothing to the entropy and its final h is dropped,
+// cbfssm.py:112,123-128,151,156), whose workgroups only write their 0.0 partial.
+__device__ __forceinline__ int bwd_segment(int y, int n0, int ny, int& run, int& k, bool& dead)
+{
+    const int n1 = ny - n0, w1 = max(0, n1 - 2);          // whole live segments of run 1: k = 2 .. n1 - 1
+    dead = false;
+    if (y < n0 - 1) { run = 0; k = y + 1; }
+    else if (y < n0 - 1 + w1) { run = 1; k = y - (n0 - 1) + 2; }
+    else if (y == n0 - 1 + w1) { run = 0; k = n0; }
+    else if (y == ny - 1) { run = 1; k = 1; dead = true; }
+    else { run = 1; k = n1; }
+    return run == 0 ? k - 1 : n0 + k - 1;
+}
 
 // doubles per saved record (one step, one 16-chain group) -- the pass kernels (writers) and the adjoint (reader) agree on it
 __host__ __device__ constexpr int saved_tile_stride(int nblk, int ksave) { return nblk * 256 * (ksave ? 2 : 1); }
@@ -1044,23 +1062,23 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void pass_kernel(PassA
     const int G16 = (N + 15) >> 4;
 
     // ---- time range of this workgroup
-    int t_first, nsteps, dir, run = 0;
+    int t_first, nsteps, dir, run = 0, slot = 0;
     const int R = a.recog_len, P = 2 * R;
     if (MODE == MODE_FWD) {
         t_first = 0; nsteps = T - 1; dir = 1;
     } else {
         int k;
-        if (int(blockIdx.y) < a.nseg0) { run = 0; k = blockIdx.y + 1; }
-        else { run = 1; k = blockIdx.y - a.nseg0 + 1; }
+        bool dead;
+        slot = bwd_segment(blockIdx.y, a.nseg0, gridDim.y, run, k, dead);
         const int o = run * R;
         const int hi = min(P * k - 1 - o, T - 1);
         const int lo = (k > 1) ? (P * (k - 1) - o) : 0;
-        t_first = hi; nsteps = hi - lo + 1; dir = -1;
+        t_first = hi; nsteps = dead ? 0 : hi - lo + 1; dir = -1;
         if (nsteps <= 0) {
             if (tid == 0) {   // partial sums are indexed per 16-chain group, whatever the kernel variant
                 const int G16p = (a.N + 15) >> 4;
                 for (int cq = 0; cq < NC; ++cq)
-                    if (gx * NC + cq < G16p) a.part_out[blockIdx.y * G16p + gx * NC + cq] = (cq == 0) ? 0.0 : 0.0;
+                    if (gx * NC + cq < G16p) a.part_out[slot * G16p + gx * NC + cq] = (cq == 0) ? 0.0 : 0.0;
             }
             return;
         }
@@ -1332,14 +1350,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void pass_kernel(PassA
     if (tid == 0) {   // partial sums are indexed per 16-chain group, whatever the kernel variant
         const int G16p = (a.N + 15) >> 4;
         for (int cq = 0; cq < NC; ++cq)
-            if (gx * NC + cq < G16p) a.part_out[blockIdx.y * G16p + gx * NC + cq] = (cq == 0) ? tot : 0.0;
+            if (gx * NC + cq < G16p) a.part_out[slot * G16p + gx * NC + cq] = (cq == 0) ? tot : 0.0;
     }
 #ifdef CBF_REV_STAMPS
 #ifndef CBF_STAMP_WAVE_PASS
 #define CBF_STAMP_WAVE_PASS (W - 1)     // the second wave whose phase shares are recorded (-DCBF_STAMP_WAVE_PASS=k picks another)
 #endif
     if (a.dbg && l == 0 && (w == 0 || w == CBF_STAMP_WAVE_PASS)) {
-        double* o = a.dbg + (int64_t(blockIdx.y) * a.gtotal + gx) * 64 + (w == 0 ? 0 : 32);
+        double* o = a.dbg + (int64_t(slot) * a.gtotal + gx) * 64 + (w == 0 ? 0 : 32);
         for (int i = 0; i < 7; ++i) { o[i] = double(st_c[i]); o[7 + i] = double(st_w[i]); }
         for (int i = 0; i < 12; ++i) o[14 + i] = double(st_m[i]);
     }
@@ -1375,23 +1393,23 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void pass_kernel_skew(
     const int gx = blockIdx.x + a.group0;
     const int c0 = gx * 32;
 
-    int t_first, nsteps, dir, run = 0;
+    int t_first, nsteps, dir, run = 0, slot = 0;
     const int R = a.recog_len, P = 2 * R;
     if (MODE == MODE_FWD) {
         t_first = 0; nsteps = T - 1; dir = 1;
     } else {
         int k;
-        if (int(blockIdx.y) < a.nseg0) { run = 0; k = blockIdx.y + 1; }
-        else { run = 1; k = blockIdx.y - a.nseg0 + 1; }
+        bool dead;
+        slot = bwd_segment(blockIdx.y, a.nseg0, gridDim.y, run, k, dead);
         const int o = run * R;
         const int hi = min(P * k - 1 - o, T - 1);
         const int lo = (k > 1) ? (P * (k - 1) - o) : 0;
-        t_first = hi; nsteps = hi - lo + 1; dir = -1;
+        t_first = hi; nsteps = dead ? 0 : hi - lo + 1; dir = -1;
         if (nsteps <= 0) {
             if (tid == 0) {   // partial sums are indexed per 16-chain group, whatever the kernel variant
                 const int G16p = (a.N + 15) >> 4;
                 for (int cq = 0; cq < 2; ++cq)
-                    if (gx * 2 + cq < G16p) a.part_out[blockIdx.y * G16p + gx * 2 + cq] = (cq == 0) ? 0.0 : 0.0;
+                    if (gx * 2 + cq < G16p) a.part_out[slot * G16p + gx * 2 + cq] = (cq == 0) ? 0.0 : 0.0;
             }
             return;
         }
@@ -1628,7 +1646,7 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void pass_kernel_skew(
     if (tid == 0) {   // partial sums are indexed per 16-chain group, whatever the kernel variant
         const int G16p = (a.N + 15) >> 4;
         for (int cq = 0; cq < 2; ++cq)
-            if (gx * 2 + cq < G16p) a.part_out[blockIdx.y * G16p + gx * 2 + cq] = (cq == 0) ? tot : 0.0;
+            if (gx * 2 + cq < G16p) a.part_out[slot * G16p + gx * 2 + cq] = (cq == 0) ? tot : 0.0;
     }
 }
 

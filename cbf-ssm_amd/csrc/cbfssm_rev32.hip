@@ -49,7 +49,7 @@ struct Rev32Args {
     double* gpart;
     int64_t slab;
     int KSr;
-    int seg0, seg1, nchunk;
+    BwdSched sched;        // bwd: the chunk of every grid.y index (as RevArgs::sched)
     int cb0;               // first Kinvbar column block this launch accumulates
     int first;             // 1: this launch also produces every other adjoint (and the y2 adjoint); 0: Kinvbar columns only
     int tri;               // 1: the products with K^-1 run as two triangular products (layout->gp_form == CBFSSM_GP_FORM_TRI)
@@ -162,10 +162,10 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void rev32_kernel(Rev3
     const int c = min(c0 + nl, N - 1);
     const bool cvalid = (c0 + nl) < N;
     const int bq = c / S;
-    const int run = (MODE == MODE_BWD) ? int(blockIdx.y) : 0;
+    const int run = (MODE == MODE_BWD) ? a.sched.run[blockIdx.y] : 0;
     const int R = a.recog_len, P = 2 * R;
     const int KSr = a.KSr;
-    const int64_t wg_linear = (int64_t(blockIdx.z) * gridDim.y + blockIdx.y) * a.gtotal + gx;
+    const int64_t wg_linear = int64_t(blockIdx.y) * a.gtotal + gx;
     const bool first = a.first != 0;
 
     bool ok[RB];
@@ -239,20 +239,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void rev32_kernel(Rev3
     for (int i = tid; i < 16 * PD; i += NT) { Fm[i] = 0.0f; Fv[i] = 0.0f; }
     __syncthreads();
 
-    // time range (as rev_kernel): forward-pass adjoint t = T-2 .. 0; backward runs: chunk z of run y covers whole
+    // time range (as rev_kernel): forward-pass adjoint t = T-2 .. 0; backward runs: the chunk of this grid.y index, whole
     // resample-to-resample segments, walked upwards in t
     int t_begin = 0, nsteps = 0;
     if (MODE == MODE_FWD) {
         nsteps = max(0, T - 1);
     } else {
-        const int o = run * R;
-        const int z = blockIdx.z, nz = a.nchunk;
-        const int nsg = a.seg1 - a.seg0;
-        const int k0 = a.seg0 + (z * nsg) / nz, k1 = a.seg0 + ((z + 1) * nsg) / nz;
-        const int tb = (k0 <= 0) ? 0 : min(T, P * k0 - o);
-        const int te = min(T, max(0, P * k1 - o));
-        t_begin = tb;
-        nsteps = max(0, te - tb);
+        t_begin = a.sched.t_begin[blockIdx.y];
+        nsteps = a.sched.nsteps[blockIdx.y];
     }
     if (MODE == MODE_FWD && nsteps > 0) {
 #pragma unroll
@@ -1014,11 +1008,11 @@ int cbfssm_backward_pass_bwd_f32(const cbfssm_problem* p, const cbfssm_pack_layo
     if (!var_x || !u || !y || !hid_b || !eps_b || !h_all || !fmv_b || !gy2 || !gpart) return fail(-1, "null pointer");
     a.cE = float(cE); a.var_x = var_x; a.u = u; a.y = y; a.eps = eps_b; a.hid = hid_b; a.h_all = h_all;
     a.gy2 = const_cast<double*>(gy2); a.gpart = gpart; a.fmv = fmv_b; a.a2s = a2s_b;
-    const int nseg = cbfssm_bwd_segments(p);
-    const int nchunk = int(cbfssm_rev_workgroups(p, 1) / (2 * ((int64_t(a.N) + 15) / 16)));      // as the float64 adjoint chunks
-    a.seg0 = 0; a.seg1 = nseg; a.nchunk = nchunk < 1 ? 1 : (nchunk > nseg ? nseg : nchunk);
+    const int nent = cbfssm_bwd_schedule(p, BWD_SCHED_CAP, a.sched.run, a.sched.t_begin, a.sched.nsteps);   // as the float64 adjoint
+    if (nent < 0) return nent;
+    if (nent == 0) return 0;                                 // T = 1 ... : no live step, no slab
     const int ncb = rev32_ncb(L->NBLK);
-    dim3 grid(unsigned(p->ngroups > 0 ? p->ngroups : (a.N + 15) / 16), 2, unsigned(a.nchunk));
+    dim3 grid((unsigned)(p->ngroups > 0 ? p->ngroups : (a.N + 15) / 16), (unsigned)nent);
     for (int cb0 = 0; cb0 < L->NBLK; cb0 += ncb) {
         a.cb0 = cb0; a.first = (cb0 == 0);
         rc = dispatch_rev32(L->NBLK, L->DK, MODE_BWD, a, grid, (hipStream_t)stream);

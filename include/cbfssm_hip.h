@@ -370,6 +370,18 @@ int cbfssm_elbo_combine_f64(const cbfssm_problem* p, double lambda0, double lamb
 int64_t cbfssm_rev_workgroups(const cbfssm_problem* p, int backward_runs);
 
 /*
+ * The schedule of the backward-run adjoint (host only, no GPU work): the live steps of both runs cut into chunks of
+ * consecutive whole resample-to-resample segments, in launch order.  Run 0 is live on t = 0 .. T-1; run 1 from
+ * t = recog_len (its segment t = recog_len-1 .. 0 reaches nothing the loss sees, cbfssm.py:112,123-128; no live step for
+ * T <= recog_len): the backward-pass kernels skip it and leave those rows of h_all, fmv_b and a2s_b unwritten.
+ * Entry i is nsteps[i] steps from t_begin[i] upwards of run[i]; every live step is in exactly one entry, nsteps is
+ * non-increasing and the table ends on single segments.  A function of (T, recog_len, B*S) only: group0 / ngroups do
+ * not enter.  Returns the number of entries (at most 32) and fills the arrays when they are given (cap: their
+ * length); cbfssm_rev_workgroups(p, 1) is that count times the chain groups.
+ */
+int cbfssm_bwd_schedule(const cbfssm_problem* p, int cap, int* run, int* t_begin, int* nsteps);
+
+/*
  * Adjoint of cbfssm_forward_pass_f64 (reverse of the tf.while_loop in CBFSSM._forward, cbfssm.py:176-237) including
  * the log-likelihood's pull on x (cbfssm.py:245-251).
  *   x, y2, eps_f, fmv_f (and a2s_f, or NULL to recompute A2) as saved by the forward evaluation; cL = loss_factors[0]/S.
@@ -401,8 +413,11 @@ int cbfssm_backward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_layo
  *             adjoint of x_{t_hi+1} from gx_carry (N,dim_x); a launch that does not end at 0 writes it there.
  *             columns used: groups * (t_hi - t_lo + 1) * 16.
  *   backward: resample-to-resample segments [seg0, seg1) of both runs (cbfssm_bwd_segments(p) in total), split over
- *             nchunk independent workgroup sets (grid.z).  gpart: groups * 2 * nchunk slabs.
+ *             nchunk <= 16 independent workgroup sets per run.  The dead steps t < recog_len of run 1 are left out
+ *             (their stash slots read as zeros).  gpart: groups * 2 * nchunk slabs.
  *             columns used: groups * 2 * nchunk * ceil((seg1-seg0)/nchunk) * 2*recog_len * 16.
+ *             nchunk = 0 with the whole range [0, cbfssm_bwd_segments(p)): the table of cbfssm_bwd_schedule, as
+ *             cbfssm_backward_pass_bwd_f64 runs it (cbfssm_rev_workgroups(p,1) slabs; not in stash mode).
  */
 int cbfssm_bwd_segments(const cbfssm_problem* p);
 int cbfssm_forward_pass_bwd_ex_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_f, const double* pack_f,
