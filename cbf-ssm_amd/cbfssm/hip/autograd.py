@@ -6,7 +6,8 @@ The CBF-SSM loss:
 
     loss = elbo_loss(engine, params, u, y, noise, condition=True)
 
-`engine` is a cbfssm.hip.train.HipElboGrad, `params` the dict of its twelve unconstrained tensors (train.PARAM_NAMES),
+`engine` is a cbfssm.hip.train.HipElboGrad, `params` the dict of its twelve unconstrained tensors (train.PARAM_NAMES) -- or a
+cbfssm.hip.train_half.HipHalfGrad (CBFSSMHALF, PR-SSM) with the tensors it names (`engine.names`) --
 `u` (B,T,dim_u) and `y` (B,T,dim_y) float64 device tensors, `noise` the dict of standard-normal draws the engine takes.
 loss.backward() then fills .grad of every parameter tensor that requires it AND of whatever produced u and y: a learnable
 input gain or bias, a sensor calibration, a feature map or an encoder in front of the model trains through the
@@ -33,11 +34,12 @@ class _ElboLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine, condition, noise, input_grads, u, y, *params):
-        pd = {k: p.detach() for k, p in zip(PARAM_NAMES, params)}
+        names = _names(engine)
+        pd = {k: p.detach() for k, p in zip(names, params)}
         want_in = bool(ctx.needs_input_grad[4] or ctx.needs_input_grad[5]) if input_grads is None else bool(input_grads)
         loss, grads, terms = engine.loss_and_grads(pd, u.detach(), y.detach(), noise, condition, input_grads=want_in)
         # (the engine's gradient tensors are views of buffers the next evaluation overwrites)
-        ctx.grads = tuple(grads[k].clone() for k in PARAM_NAMES)
+        ctx.grads = tuple(grads[k].clone() for k in names)
         ctx.gu = grads['u'].clone() if want_in else None
         ctx.gy = grads['y'].clone() if want_in else None
         ctx.shapes = tuple(p.shape for p in params)
@@ -52,17 +54,23 @@ class _ElboLoss(torch.autograd.Function):
         return (None, None, None, None, gu, gy) + gp
 
 
+def _names(engine):
+    """the engine's parameter names: a forward-only engine lists its own, HipElboGrad has the twelve of CBFSSM"""
+    return getattr(engine, 'names', None) or PARAM_NAMES
+
+
 def elbo_loss(engine, params, u, y, noise, condition=True, input_grads=None):
     """The loss of one mini-batch as a 0-d tensor with a grad_fn (see the module docstring).
 
     input_grads: None -- d loss / d u and d loss / d y are computed when u or y requires grad; True -- always; False --
     never (u and y get no gradient; loss and parameter gradients are those of engine.loss_and_grads as it always was)."""
-    missing = [k for k in PARAM_NAMES if k not in params]
+    names = _names(engine)
+    missing = [k for k in names if k not in params]
     if missing:
         raise KeyError('elbo_loss: params lacks %s' % ', '.join(missing))
     if input_grads is False and (getattr(u, 'requires_grad', False) or getattr(y, 'requires_grad', False)):
         u, y = u.detach(), y.detach()
-    return _ElboLoss.apply(engine, bool(condition), noise, input_grads, u, y, *[params[k] for k in PARAM_NAMES])
+    return _ElboLoss.apply(engine, bool(condition), noise, input_grads, u, y, *[params[k] for k in names])
 
 
 # ---- one sparse GP: GPModel.predict and GPModel.prior_kl (gp_tf.py:132-172) as torch functions -------------------------

@@ -33,6 +33,8 @@ SYMBOLS = (
     'cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_f64', 'cbfssm_gp_rollout_bwd_workgroups', 'cbfssm_gp_rollout_bwd_work_elems',
     'cbfssm_gp_rollout_bwd_f64',
     'cbfssm_rigid_filter_partials', 'cbfssm_rigid_filter_f64', 'cbfssm_rigid_filter_bwd_f64',
+    'cbfssm_gru_recog_bwd_in_f64', 'cbfssm_conv_recog_bwd_in_f32', 'cbfssm_half_forward_pass_bwd_in_f64',
+    'cbfssm_half_input_grads_f64',
 )
 
 
@@ -180,6 +182,11 @@ def load():
     lib.cbfssm_rigid_filter_partials.argtypes = [i64]
     lib.cbfssm_rigid_filter_f64.argtypes = [C.POINTER(RigidBody)] + [vp] * 6 + [i64, i64] + [vp] * 3
     lib.cbfssm_rigid_filter_bwd_f64.argtypes = [C.POINTER(RigidBody)] + [vp] * 9 + [i64, i64] + [vp] * 5
+    lib.cbfssm_gru_recog_bwd_in_f64.argtypes = [ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cbfssm_conv_recog_bwd_in_f32.argtypes = [ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp]
+    lib.cbfssm_half_forward_pass_bwd_in_f64.argtypes = ([C.POINTER(Problem), C.POINTER(PackLayout)] + [vp] * 9 +
+                                                        [dbl, vp, vp, ip, ip, vp, vp, vp, i64, vp, vp, vp])
+    lib.cbfssm_half_input_grads_f64.argtypes = [C.POINTER(Problem), C.POINTER(PackLayout)] + [vp] * 8 + [ip, dbl, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith('_elems'):                 # element counts: 64-bit results (set above)

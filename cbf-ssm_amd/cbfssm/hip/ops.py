@@ -454,9 +454,22 @@ class TimeLoops:
             rc = lib.cbfssm_half_forward_pass_bwd_f32(*a, st)
         else:
             t_hi, t_lo, sa, sk, cols = chunk or (q.T - 2, 0, None, None, 0)
-            rc = lib.cbfssm_half_forward_pass_bwd_f64(*a, t_hi, t_lo, _ptr(ws.gx_carry) if chunk else None, _ptr(sa),
-                                                      _ptr(sk), cols, st)
+            r = (t_hi, t_lo, _ptr(ws.gx_carry) if chunk else None, _ptr(sa), _ptr(sk), cols)
+            if self.in_bufs is not None:
+                _l.check(lib.cbfssm_half_forward_pass_bwd_in_f64(*a, *r, _ptr(self.in_bufs[0]), _ptr(self.in_bufs[2]), st),
+                         'cbfssm_half_forward_pass_bwd_in_f64')
+                return
+            rc = lib.cbfssm_half_forward_pass_bwd_f64(*a, *r, st)
         self._check(rc, 'half_forward_pass_bwd')
+
+    def half_input_grads(self, gx0, gwin, recog_len, grad_u, grad_y, st):
+        """d loss / d u, d loss / d y of a forward-only variant (cbfssm_half_input_grads_f64): gx0 for the `output` recogniser,
+        gwin (B, recog_len, dim_u + dim_y) for rnn / conv -- exactly one of them"""
+        ws, (gin_f, _, gyo) = self.ws, self.in_bufs
+        _l.check(_l.load().cbfssm_half_input_grads_f64(C.byref(self.prob), C.byref(self.pack_f.layout), _ptr(self.pack_f.buf),
+                                                       _ptr(self.var_y), _ptr(self.y), _ptr(ws.x), _ptr(gin_f), _ptr(gyo),
+                                                       _ptr(gx0), _ptr(gwin), int(recog_len), self.cL, _ptr(grad_u),
+                                                       _ptr(grad_y), st), 'cbfssm_half_input_grads_f64')
 
     def elbo_tail(self, lf0, lf1, st, kl_pack=None):
         """log-likelihood + predictive moments, then ws.out = [loglik, kl_x, entropy, kl_z_f, kl_z_b, elbo, loss, info];

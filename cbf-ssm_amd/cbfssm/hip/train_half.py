@@ -289,7 +289,35 @@ class HipHalfGrad:
         loss, terms = self._terms(ws, red2)
         return loss, terms, ws
 
-    def loss_and_grads(self, params, u, y, noise, condition=True, weight=1.0, local=False):
+    def _need_input_grads(self):
+        if self.f32:
+            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) exist for float64 engines only: the '
+                                      'float32 adjoint kernel keeps no data rows of the input adjoint')
+        if self.dist is not None:
+            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) are not available under a process '
+                                      'group: evaluate the shard on an engine without one')
+
+    def _input_buffers(self, prob, ws, R):
+        """per-chain buffers of the `_in` adjoint (gin_f, -, gyo), the window adjoint and the two results, kept with the
+        workspace"""
+        if getattr(ws, 'in_bufs', None) is None:
+            lib = _l.load()
+            f = dict(dtype=torch.float64, device=self.device)
+            n_f, n_o = (int(fn(C.byref(prob))) for fn in (lib.cbfssm_input_adjoint_fwd_elems, lib.cbfssm_input_adjoint_obs_elems))
+            assert min(n_f, n_o) >= 0, (n_f, n_o)
+            ws.in_bufs = (torch.zeros(max(n_f, 1), **f), None, torch.zeros(max(n_o, 1), **f))
+            ws.gwin = torch.zeros(prob.B, R, prob.dim_u + prob.dim_y, **f)
+            ws.grad_u = torch.zeros(prob.B, prob.T, prob.dim_u, **f)
+            ws.grad_y = torch.zeros(prob.B, prob.T, prob.dim_y, **f)
+        return ws.in_bufs
+
+    def loss_and_grads(self, params, u, y, noise, condition=True, weight=1.0, local=False, input_grads=False):
+        """input_grads: the grads also hold 'u' (B,T,dim_u) and 'y' (B,T,dim_y), the gradient of the loss with respect to the
+        input and output sequences (tf.gradients(loss, sample_in / sample_out)): through the time loop, the log-likelihood
+        and the recognition model's window.  float64 engines without a process group only; an eager path (HipHalfTrainStep
+        never takes it)."""
+        if input_grads:
+            self._need_input_grads()
         lib = _l.load()
         dev = self.device
         p = {k: _f64(params[k], dev) for k in self.names}
@@ -303,6 +331,8 @@ class HipHalfGrad:
         rp = {}
         rnames = self._recog_params(p)
         gru = conv = None
+        R = min(int(self.config['recog_len']), T)
+        win = ()
         if self.fused_gru:
             rflat = self._recog_flat(params, p)
             gru = self._gru_forward(rflat, u, y, keep=True)
@@ -313,11 +343,15 @@ class HipHalfGrad:
             x0 = conv['x0']
         elif rnames:
             rp = {k: p[k].detach().clone().requires_grad_(True) for k in rnames}
-            x0g = self._recog(rp, u, y)
+            if input_grads:     # the window's adjoint comes from the tensor library's autograd too
+                win = tuple(t[:, :R].detach().clone().requires_grad_(True) for t in (u, y))
+            x0g = self._recog(rp, *(win or (u, y)))
             x0 = x0g.detach().contiguous()
         else:
             x0 = self._x0(p, u, y).contiguous()
         lp = self._loops(prob, ws, c, u, y, x0, eps_f)
+        if input_grads:
+            lp.in_bufs = self._input_buffers(prob, ws, R)
         self._forward(lp, p, c)
 
         st = _stream()
@@ -375,17 +409,24 @@ class HipHalfGrad:
                  'cbfssm_data_tail_f64')
         gx0_b = ws.gx0.view(B, self.S, self.dim_x).sum(1)        # d loss / d x_0 per sequence (tiled over S, :87)
         rgrads = {}
+        gwin = ws.gwin if input_grads and rnames else None
         if gru is not None or conv is not None:
             if gru is not None:
                 P, gpart = gru['P'], gru['gpart']
-                rc = lib.cbfssm_gru_recog_bwd_f64(B, T, self.dim_u, self.dim_y, self.dim_x, min(int(self.config['recog_len']), T), _ptr(u),
-                                                  _ptr(y), _ptr(rflat), _ptr(gru['act']), _ptr(gx0_b.contiguous()), _ptr(gpart), st)
-                _l.check(rc, 'cbfssm_gru_recog_bwd_f64')
+                a = (B, T, self.dim_u, self.dim_y, self.dim_x, R, _ptr(u), _ptr(y), _ptr(rflat), _ptr(gru['act']),
+                     _ptr(gx0_b.contiguous()), _ptr(gpart))
+                if input_grads:
+                    _l.check(lib.cbfssm_gru_recog_bwd_in_f64(*a, _ptr(gwin), st), 'cbfssm_gru_recog_bwd_in_f64')
+                else:
+                    _l.check(lib.cbfssm_gru_recog_bwd_f64(*a, st), 'cbfssm_gru_recog_bwd_f64')
             else:
                 P, gpart = conv['P'], conv['gpart']
-                rc = lib.cbfssm_conv_recog_bwd_f32(B, T, self.dim_u, self.dim_y, self.dim_x, conv['R'], _ptr(u), _ptr(y), _ptr(rflat),
-                                                   _ptr(gx0_b.contiguous()), _ptr(gpart), st)
-                _l.check(rc, 'cbfssm_conv_recog_bwd_f32')
+                a = (B, T, self.dim_u, self.dim_y, self.dim_x, conv['R'], _ptr(u), _ptr(y), _ptr(rflat),
+                     _ptr(gx0_b.contiguous()), _ptr(gpart))
+                if input_grads:
+                    _l.check(lib.cbfssm_conv_recog_bwd_in_f32(*a, _ptr(gwin), st), 'cbfssm_conv_recog_bwd_in_f32')
+                else:
+                    _l.check(lib.cbfssm_conv_recog_bwd_f32(*a, st), 'cbfssm_conv_recog_bwd_f32')
             rg = torch.zeros(P, dtype=torch.float64, device=dev)
             ops.reduce_partials(gpart, P, B, rg, st)
             o = 0
@@ -393,8 +434,13 @@ class HipHalfGrad:
                 rgrads[k] = rg[o:o + p[k].numel()].view(p[k].shape)
                 o += p[k].numel()
         elif rnames:
-            gl = torch.autograd.grad(x0g, [rp[k] for k in rnames], grad_outputs=gx0_b)
+            gl = torch.autograd.grad(x0g, [rp[k] for k in rnames] + list(win), grad_outputs=gx0_b)
             rgrads = dict(zip(rnames, gl))
+            if input_grads:
+                gwin.copy_(torch.cat(gl[len(rnames):], dim=2))
+        if input_grads:
+            # x_0 = [y_0, 0] without a recognition model: its adjoint goes to y_0 directly
+            lp.half_input_grads(None if rnames else ws.gx0, gwin, R, ws.grad_u, ws.grad_y, st)
         if self.dist is not None and not local:
             # one flat buffer per step: [slab | data scalars | stash-mode K^-1-adjoint image | recognition-model gradients]
             pieces = [red] + ([gB] if gB is not None else []) + [rgrads[k].reshape(-1) for k in rnames]
@@ -436,6 +482,8 @@ class HipHalfGrad:
                 gall[o:o + rgrads[k].numel()] = rgrads[k].reshape(-1)
                 grads[k] = gall[o:o + rgrads[k].numel()].view(rgrads[k].shape)
                 o += rgrads[k].numel()
+            if input_grads:
+                grads['u'], grads['y'] = ws.grad_u, ws.grad_y
             return loss, grads, terms
 
         grads = dict(rgrads)
@@ -454,6 +502,8 @@ class HipHalfGrad:
         grads[pre + 'lengthscales_unc'] = gls * torch.sigmoid(lsu)
         grads['var_x_unc'] = small[0:self.dim_x] * torch.sigmoid(p['var_x_unc'])
         grads['var_y_unc'] = (small[16:16 + self.dim_y] + tail[3:]) * torch.sigmoid(p['var_y_unc'])
+        if input_grads:
+            grads['u'], grads['y'] = ws.grad_u, ws.grad_y
         return loss, grads, terms
 
 

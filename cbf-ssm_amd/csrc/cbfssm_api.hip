@@ -782,6 +782,70 @@ __global__ void input_grads_kernel(InGradArgs a)
     }
 }
 
+// The same for the forward-only variants (problem->half): no backward GP; the window [u, y][:, :recog_len] also reaches the
+// loss through x_0 (gwin: the recognition kernels' window adjoint; gx0: x_0 = [y_0, 0], the `output` recogniser).  Row 0 of
+// gyo is never read (x_0 is not y_tilde[0] here); the log-likelihood covers every row (cbfssmhalf.py:174-189, prssm.py:96).
+struct HalfInGradArgs {
+    int B, S, T, dim_x, dim_u, dim_y, R;
+    const double* gin_f;   // (T-1, dim_u, N)
+    const double* gyo;     // (T, dim_y, N), rows t >= 1
+    const double* gx0;     // (N, dim_x) or null
+    const double* gwin;    // (B, R, dim_u + dim_y) or null
+    const double* invl_f;
+    const double* x;       // (T, N, dim_x)
+    const double* y;       // (B, T, dim_y)
+    const double* var_y;
+    double cL;
+    double* gu;
+    double* gy;
+};
+
+__global__ void half_input_grads_kernel(HalfInGradArgs a)
+{
+    const int64_t nu = int64_t(a.B) * a.T * a.dim_u, ny = int64_t(a.B) * a.T * a.dim_y;
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= nu + ny) return;
+    const int64_t N = int64_t(a.B) * a.S;
+    const int n_in = a.dim_u + a.dim_y;
+    const bool is_u = i < nu;
+    const int nd = is_u ? a.dim_u : a.dim_y;
+    const int64_t e = is_u ? i : i - nu;
+    const int k = int(e % nd);
+    const int t = int((e / nd) % a.T);
+    const int b = int(e / (int64_t(nd) * a.T));
+    const bool in_win = a.gwin && t < a.R;
+    const double* pw = in_win ? a.gwin + (int64_t(b) * a.R + t) * n_in : nullptr;
+    if (is_u) {
+        double r = 0.0;
+        if (t < a.T - 1) {
+            const double* pf = a.gin_f + (int64_t(t) * a.dim_u + k) * N + int64_t(b) * a.S;
+            double sf = 0.0;
+            for (int s = 0; s < a.S; ++s) sf += pf[s];
+            r = a.invl_f[a.dim_x + k] * sf;
+        }
+        if (in_win) r += pw[k];
+        a.gu[e] = r;
+    } else {
+        const double* px = a.x + (int64_t(t) * N + int64_t(b) * a.S) * a.dim_x + k;
+        const double yv = a.y[e];
+        double so = 0.0, sl = 0.0;
+        if (t >= 1) {
+            const double* po = a.gyo + (int64_t(t) * a.dim_y + k) * N + int64_t(b) * a.S;
+            for (int s = 0; s < a.S; ++s) so += po[s];
+        }
+        for (int s = 0; s < a.S; ++s) sl += yv - px[int64_t(s) * a.dim_x];
+        double r = so + a.cL * sl / a.var_y[k];
+        if (in_win) r += pw[a.dim_u + k];
+        if (a.gx0 && t == 0) {
+            const double* p0 = a.gx0 + int64_t(b) * a.S * a.dim_x + k;
+            double s0 = 0.0;
+            for (int s = 0; s < a.S; ++s) s0 += p0[int64_t(s) * a.dim_x];
+            r += s0;
+        }
+        a.gy[e] = r;
+    }
+}
+
 __global__ void reduce_partials_kernel(const double* gpart, int64_t slab, int nwg, double* out)
 {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1470,7 +1534,6 @@ static int forward_pass_bwd_impl(const cbfssm_problem* p, const cbfssm_pack_layo
     a.gpart = gpart; a.t_hi = t_hi; a.t_lo = t_lo; a.gx_carry = gx_carry;
     a.half = p->half; a.gx0 = gx0;
     if (input_grads) {
-        if (p->half) return fail(-1, "input gradients: not for the forward-only variants");
         if ((p->dim_u > 0 && p->T > 1 && !gin_f) || (p->dim_y > 0 && !gyo)) return fail(-1, "gin_f/gyo is null");
         a.gin = gin_f; a.gyo = gyo;
     }
@@ -1524,6 +1587,18 @@ int cbfssm_half_forward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_
     if (!p || !p->half) return fail(-1, "problem->half must be 1");
     return forward_pass_bwd_impl(p, L, pack_f, var_x, var_y, u, y, nullptr, eps_f, x, fmv_f, a2s_f, cL, nullptr, gx0, gpart,
                                  t_hi, t_lo, gx_carry, stash_a, stash_k, stash_ld, stream);
+}
+
+int cbfssm_half_forward_pass_bwd_in_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_f,
+                                        const double* var_x, const double* var_y, const double* u, const double* y,
+                                        const double* eps_f, const double* x, const double* fmv_f, const double* a2s_f,
+                                        double cL, double* gx0, double* gpart, int t_hi, int t_lo, double* gx_carry,
+                                        double* stash_a, double* stash_k, int64_t stash_ld, double* gin_f, double* gyo,
+                                        void* stream)
+{
+    if (!p || !p->half) return fail(-1, "problem->half must be 1");
+    return forward_pass_bwd_impl(p, L, pack_f, var_x, var_y, u, y, nullptr, eps_f, x, fmv_f, a2s_f, cL, nullptr, gx0, gpart,
+                                 t_hi, t_lo, gx_carry, stash_a, stash_k, stash_ld, stream, gin_f, gyo, true);
 }
 
 int cbfssm_forward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_f,
@@ -1672,6 +1747,29 @@ int cbfssm_input_grads_f64(const cbfssm_problem* p, const cbfssm_pack_layout* la
     if (total <= 0) return 0;
     hipLaunchKernelGGL(input_grads_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("input_grads");
+}
+
+int cbfssm_half_input_grads_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_f, const double* pack_f,
+                                const double* var_y, const double* y, const double* x, const double* gin_f, const double* gyo,
+                                const double* gx0, const double* gwin, int recog_len, double cL, double* grad_u, double* grad_y,
+                                void* stream)
+{
+    int rc = check_problem(p, layout_f, p ? p->dim_x : 0);
+    if (rc) return rc;
+    if (!p->half) return fail(-1, "problem->half must be 1");
+    if (p->dim_y < 1) return fail(-1, "bad dim_y/dim_u");
+    if (!pack_f || !var_y || !y || !x || !gyo || !grad_y) return fail(-1, "null pointer");
+    if (p->dim_u > 0 && (!grad_u || (p->T > 1 && !gin_f))) return fail(-1, "null pointer");
+    if (!gx0 == !gwin) return fail(-1, "exactly one of gx0 (output recogniser) and gwin (rnn / conv) must be given");
+    if (gwin && (recog_len < 1 || recog_len > p->T)) return fail(-1, "recog_len must be in [1, T]");   // (unused with gx0)
+    HalfInGradArgs a;
+    a.B = p->B; a.S = p->S; a.T = p->T; a.dim_x = p->dim_x; a.dim_u = p->dim_u; a.dim_y = p->dim_y; a.R = recog_len;
+    a.gin_f = gin_f; a.gyo = gyo; a.gx0 = gx0; a.gwin = gwin;
+    a.invl_f = pack_f + layout_f->invl;
+    a.x = x; a.y = y; a.var_y = var_y; a.cL = cL; a.gu = grad_u; a.gy = grad_y;
+    const int64_t total = int64_t(p->B) * p->T * (p->dim_u + p->dim_y);
+    hipLaunchKernelGGL(half_input_grads_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("half_input_grads");
 }
 
 int cbfssm_backward_pass_bwd_f64(const cbfssm_problem* p, const cbfssm_pack_layout* L, const double* pack_b,

@@ -36,6 +36,7 @@ struct GruArgs {
     const double* gx0;    // [B][dim_x]   d loss / d x_0
     double* gpart;        // [B][P]       per-sequence gradient slabs, the six tensors behind each other
     int64_t P;
+    double* gwin;         // [B][R][n_in] d loss / d window [u, y][:, :R] in sequence time order, or null (weights only)
 };
 
 __device__ __forceinline__ double sigm(double x) { return 1.0 / (1.0 + exp(-x)); }
@@ -90,7 +91,10 @@ __global__ __launch_bounds__(64) void gru_forward_kernel(GruArgs a)
     }
 }
 
-// reverse mode through the dense layer and the recog_len GRU steps of one sequence
+// reverse mode through the dense layer and the recog_len GRU steps of one sequence.  IN: also the adjoint of the window
+// (GruArgs::gwin) -- a template flag, not a test of the pointer: with the test in the one kernel the default CBFSSMHALF train
+// step measured 6 us slower than its parent (profiles/half_input_gradients/), so the weights-only kernel stays the code it was
+template <bool IN>
 __global__ __launch_bounds__(64) void gru_backward_kernel(GruArgs a)
 {
     __shared__ double xs[GRU_MAXIN], hp[GRU_H], rs[GRU_H], dcp[GRU_H], dgp[2 * GRU_H], dhs[GRU_H], gxs[GRU_H];
@@ -163,6 +167,13 @@ __global__ __launch_bounds__(64) void gru_backward_kernel(GruArgs a)
             for (int j = 0; j < 2 * GRU_H; ++j) dhn = fma(a.Wg[(n_in + l) * 32 + j], dgp[j], dhn);
             dh = dhn;
         }
+        if (IN && l < n_in) {
+            // the step's input x = [u, y][R - 1 - step] enters both pre-activations: gates first, ascending j
+            double gx = 0.0;
+            for (int j = 0; j < 2 * GRU_H; ++j) gx = fma(a.Wg[l * 32 + j], dgp[j], gx);
+            for (int j = 0; j < GRU_H; ++j) gx = fma(a.Wc[l * 16 + j], dcp[j], gx);
+            a.gwin[(int64_t(b) * a.R + (a.R - 1 - step)) * n_in + l] = gx;
+        }
         __syncthreads();                                                      // the shared vectors are rewritten above
     }
 #pragma unroll
@@ -193,7 +204,7 @@ static int fill_gru(GruArgs& a, int B, int T, int dim_u, int dim_y, int dim_x, i
     a.Wg = params; a.bg = a.Wg + int64_t(nrow) * 32; a.Wc = a.bg + 32; a.bc = a.Wc + int64_t(nrow) * 16;
     a.Wd = a.bc + 16; a.bd = a.Wd + int64_t(GRU_H) * dim_x;
     a.P = int64_t(nrow) * 48 + 48 + int64_t(GRU_H) * dim_x + dim_x;
-    a.x0 = nullptr; a.act = nullptr; a.gx0 = nullptr; a.gpart = nullptr;
+    a.x0 = nullptr; a.act = nullptr; a.gx0 = nullptr; a.gpart = nullptr; a.gwin = nullptr;
     return 0;
 }
 
@@ -220,6 +231,7 @@ struct ConvArgs {
     const double* gx0;    // [B][dim_x]   d loss / d x_0
     double* gpart;        // [B][E]       per-sequence gradient slabs, the four tensors behind each other
     int64_t E;
+    double* gwin;         // [B][R][n_in] d loss / d window [u, y][:, :R], or null (weights only)
 };
 
 struct ConvShared {
@@ -279,6 +291,7 @@ __global__ __launch_bounds__(64) void conv_forward_kernel(ConvArgs a)
     if (l < a.dim_x) a.x0[int64_t(b) * a.dim_x + l] = double(v);
 }
 
+template <bool IN>      // IN: also the adjoint of the window (ConvArgs::gwin); a template flag like the GRU kernel's
 __global__ __launch_bounds__(64) void conv_backward_kernel(ConvArgs a)
 {
     __shared__ ConvShared s;
@@ -317,6 +330,19 @@ __global__ __launch_bounds__(64) void conv_backward_kernel(ConvArgs a)
         for (int t = 0; t < npre; ++t) g += s.gpre[t * CONV_F + l];
         gbc[l] = double(g);
     }
+    // window entry (t, i): conv position t - w reads it through tap w (the casts' adjoint is the identity)
+    if (IN) {
+        for (int e = l; e < a.R * n_in; e += 64) {
+            const int t = e / n_in, i = e - t * n_in;
+            float g = 0.0f;
+            for (int w = 0; w < CONV_W; ++w) {
+                const int pos = t - w;
+                if (pos < 0 || pos >= npre) continue;
+                for (int f = 0; f < CONV_F; ++f) g = fmaf(s.K[(w * n_in + i) * CONV_F + f], s.gpre[pos * CONV_F + f], g);
+            }
+            a.gwin[int64_t(b) * a.R * n_in + e] = double(g);
+        }
+    }
 }
 
 static int64_t conv_elems(int dim_u, int dim_y, int dim_x, int recog_len)
@@ -348,7 +374,7 @@ static int fill_conv(ConvArgs& a, int B, int T, int dim_u, int dim_y, int dim_x,
     a.u = u; a.y = y;
     a.K = params; a.bc = a.K + CONV_W * n_in * CONV_F; a.Wd = a.bc + CONV_F; a.bd = a.Wd + CONV_F * a.P * dim_x;
     a.E = conv_elems(dim_u, dim_y, dim_x, recog_len);
-    a.x0 = nullptr; a.gx0 = nullptr; a.gpart = nullptr;
+    a.x0 = nullptr; a.gx0 = nullptr; a.gpart = nullptr; a.gwin = nullptr;
     return 0;
 }
 
@@ -383,17 +409,32 @@ int cbfssm_gru_recog_f64(int B, int T, int dim_u, int dim_y, int dim_x, int reco
     return e == hipSuccess ? 0 : fail(-int(e) - 1000, "gru forward launch failed");
 }
 
-int cbfssm_gru_recog_bwd_f64(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
-                             const double* params, const double* act, const double* gx0, double* gpart, void* stream)
+static int gru_backward(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                        const double* params, const double* act, const double* gx0, double* gpart, double* gwin,
+                        bool want_in, void* stream)
 {
     GruArgs a;
     int rc = fill_gru(a, B, T, dim_u, dim_y, dim_x, recog_len, u, y, params);
     if (rc) return rc;
-    if (!act || !gx0 || !gpart) return fail(-1, "null pointer");
-    a.act = const_cast<double*>(act); a.gx0 = gx0; a.gpart = gpart;
-    hipLaunchKernelGGL(gru_backward_kernel, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
+    if (!act || !gx0 || !gpart || (want_in && !gwin)) return fail(-1, "null pointer");
+    a.act = const_cast<double*>(act); a.gx0 = gx0; a.gpart = gpart; a.gwin = gwin;
+    if (want_in) hipLaunchKernelGGL(gru_backward_kernel<true>, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(gru_backward_kernel<false>, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail(-int(e) - 1000, "gru backward launch failed");
+}
+
+int cbfssm_gru_recog_bwd_f64(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                             const double* params, const double* act, const double* gx0, double* gpart, void* stream)
+{
+    return gru_backward(B, T, dim_u, dim_y, dim_x, recog_len, u, y, params, act, gx0, gpart, nullptr, false, stream);
+}
+
+int cbfssm_gru_recog_bwd_in_f64(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                                const double* params, const double* act, const double* gx0, double* gpart, double* gwin,
+                                void* stream)
+{
+    return gru_backward(B, T, dim_u, dim_y, dim_x, recog_len, u, y, params, act, gx0, gpart, gwin, true, stream);
 }
 
 int64_t cbfssm_conv_recog_param_elems(int dim_u, int dim_y, int dim_x, int recog_len)
@@ -415,17 +456,30 @@ int cbfssm_conv_recog_f32(int B, int T, int dim_u, int dim_y, int dim_x, int rec
     return e == hipSuccess ? 0 : fail(-int(e) - 1000, "conv recognition forward launch failed");
 }
 
-int cbfssm_conv_recog_bwd_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
-                              const double* params, const double* gx0, double* gpart, void* stream)
+static int conv_backward(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                         const double* params, const double* gx0, double* gpart, double* gwin, bool want_in, void* stream)
 {
     ConvArgs a;
     int rc = fill_conv(a, B, T, dim_u, dim_y, dim_x, recog_len, u, y, params);
     if (rc) return rc;
-    if (!gx0 || !gpart) return fail(-1, "null pointer");
-    a.gx0 = gx0; a.gpart = gpart;
-    hipLaunchKernelGGL(conv_backward_kernel, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
+    if (!gx0 || !gpart || (want_in && !gwin)) return fail(-1, "null pointer");
+    a.gx0 = gx0; a.gpart = gpart; a.gwin = gwin;
+    if (want_in) hipLaunchKernelGGL(conv_backward_kernel<true>, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(conv_backward_kernel<false>, dim3(unsigned(B)), dim3(64), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail(-int(e) - 1000, "conv recognition backward launch failed");
+}
+
+int cbfssm_conv_recog_bwd_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                              const double* params, const double* gx0, double* gpart, void* stream)
+{
+    return conv_backward(B, T, dim_u, dim_y, dim_x, recog_len, u, y, params, gx0, gpart, nullptr, false, stream);
+}
+
+int cbfssm_conv_recog_bwd_in_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                                 const double* params, const double* gx0, double* gpart, double* gwin, void* stream)
+{
+    return conv_backward(B, T, dim_u, dim_y, dim_x, recog_len, u, y, params, gx0, gpart, gwin, true, stream);
 }
 
 }  // extern "C"

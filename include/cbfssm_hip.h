@@ -662,6 +662,54 @@ int cbfssm_conv_recog_f32(int B, int T, int dim_u, int dim_y, int dim_x, int rec
 int cbfssm_conv_recog_bwd_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
                               const double* params, const double* gx0, double* gpart, void* stream);
 
+/*
+ * ---- input gradients of the forward-only variants (CBFSSMHALF, PR-SSM): d loss / d u (B,T,dim_u), d loss / d y (B,T,dim_y).
+ * Replaces tf.gradients(model.loss, model.sample_in) and tf.gradients(model.loss, model.sample_out) on the graphs of
+ * cbfssm/model/cbfssmhalf.py:82-93,117-199 and cbfssm/model/prssm.py:96-157 (placeholders: base_model.py:22-27).  float64 only.
+ * There u and y reach the loss three ways: through gp_f's input and the Kalman update in the time loop, through the
+ * log-likelihood, and through x_0, the recognition model's output over the window [u, y][:, :recog_len].
+ *
+ * cbfssm_gru_recog_bwd_in_f64 / cbfssm_conv_recog_bwd_in_f32: the recognition backward calls above (same arguments, the
+ * same kernel source with the window adjoint compiled in, the same bits in gpart) which also write gwin (B, recog_len, dim_u + dim_y): the adjoint of the window, row t
+ * in SEQUENCE time order (cbfssmhalf.py:86 reverses the window for the GRU; not here), u columns first.  Every entry is
+ * written exactly once, no atomics.  GRU (float64): per step, gx[i] = sum_j W_g[i][j] dgp[j] + sum_j W_c[i][j] dcp[j] over the
+ * gate and candidate pre-activation adjoints.  conv (float32 arithmetic, prssm.py:146-157; the adjoint of the casts is the
+ * identity): gx[t][i] = sum_w sum_f K[w][i][f] dpre[t - w][f] over the valid taps, dpre the pre-activation adjoint (the pooled
+ * adjoint at the pooling winner where its pre-activation is positive, else 0: relu'(0) = 0, a tie goes to the first element).
+ * Limits and return codes as for the calls above; gwin must not be NULL.
+ *
+ * cbfssm_half_forward_pass_bwd_in_f64: cbfssm_half_forward_pass_bwd_f64 (cbfssmhalf.py:117-172, prssm.py:96-118) through
+ * the input-gradient instantiations of the adjoint kernel, as cbfssm_forward_pass_bwd_in_f64 is to the `_ex` form: also
+ * writes gin_f (cbfssm_input_adjoint_fwd_elems doubles, (T-1, dim_u, N)) and the rows t >= 1 of gyo
+ * (cbfssm_input_adjoint_obs_elems doubles, (T, dim_y, N); zeros where a step does not condition, i.e. everywhere for
+ * PR-SSM).  Row 0 of gyo is not written: x_0 is the recognition output here, its adjoint leaves as gx0.
+ *
+ * cbfssm_half_input_grads_f64: one launch after the adjoint and the recognition backward call, one thread per entry, the S
+ * particles summed in particle order, terms added in this order:
+ *   grad_u[b,t,k] = [t <= T-2] 1/l_f[dim_x+k] sum_s gin_f[t][k][bS+s]  +  [t < recog_len, gwin] gwin[b][t][k]
+ *   grad_y[b,t,d] = [t >= 1] sum_s gyo[t][d][bS+s]  +  cL sum_s (y[b,t,d] - x[t,bS+s,d]) / var_y[d]      (all T rows:
+ *                   cbfssmhalf.py:174-189, prssm.py:96)  +  [t < recog_len, gwin] gwin[b][t][dim_u+d]
+ *                   +  [t = 0, gx0] sum_s gx0[bS+s][d]
+ * Exactly one of gx0 (the `output` recogniser: x_0 = [y_0, 0]; the adjoint pass's (N, dim_x) buffer) and gwin (rnn / conv;
+ * recog_len = its row count, 1 <= recog_len <= T) is not NULL.  cL: lambda_0 / S for CBFSSMHALF, lambda_0 for PR-SSM.
+ * grad_u may be NULL when dim_u = 0.  Fixed order, no atomics: two evaluations are bitwise identical.
+ */
+int cbfssm_gru_recog_bwd_in_f64(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                                const double* params, const double* act, const double* gx0, double* gpart, double* gwin,
+                                void* stream);
+int cbfssm_conv_recog_bwd_in_f32(int B, int T, int dim_u, int dim_y, int dim_x, int recog_len, const double* u, const double* y,
+                                 const double* params, const double* gx0, double* gpart, double* gwin, void* stream);
+int cbfssm_half_forward_pass_bwd_in_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_f, const double* pack_f,
+                                        const double* var_x, const double* var_y, const double* u, const double* y,
+                                        const double* eps_f, const double* x, const double* fmv_f, const double* a2s_f,
+                                        double cL, double* gx0, double* gpart, int t_hi, int t_lo, double* gx_carry,
+                                        double* stash_a, double* stash_k, int64_t stash_ld, double* gin_f, double* gyo,
+                                        void* stream);
+int cbfssm_half_input_grads_f64(const cbfssm_problem* p, const cbfssm_pack_layout* layout_f, const double* pack_f,
+                                const double* var_y, const double* y, const double* x, const double* gin_f, const double* gyo,
+                                const double* gx0, const double* gwin, int recog_len, double cL, double* grad_u, double* grad_y,
+                                void* stream);
+
 /* The rank-local data terms of the flat reduce buffer: tail[0..2] = loglik, kl_x, entropy (from the ELBO combination's
  * out[0..2]); tail[3 + d] = d loss / d var_y[d] through the log-likelihood (cbfssm.py:245-251), d < dim_y, from the
  * per-dimension totals of ll_part (cbfssm_loglik_moments_f64).  cL = loss_factors[0] / S. */
