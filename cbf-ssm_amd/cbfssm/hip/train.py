@@ -131,6 +131,29 @@ def kgk_image(pack, slab, img=None):
     return Bd.view(nb, 4, 4, nb, 16).permute(0, 3, 1, 2, 4).reshape(-1)
 
 
+def need_input_grads(f32, dist):
+    """refuse d loss / d u, d loss / d y where no engine delivers them (HipElboGrad and HipHalfGrad alike)"""
+    if f32:
+        raise NotImplementedError('input gradients (d loss / d u, d loss / d y) exist for float64 engines only: the '
+                                  'float32 adjoint kernel keeps no data rows of the input adjoint')
+    if dist is not None:
+        raise NotImplementedError('input gradients (d loss / d u, d loss / d y) are not available under a process '
+                                  'group: evaluate the shard on an engine without one')
+
+
+def gp_unc_grads(pre, p, gz, gmu, gs2, gvar, gls, shared_ls=False):
+    """tensor-library tail: the chain through the positivity transforms of one GP's five tensors p[pre + name], given the
+    adjoints of the constrained ones (_gp_adjoint).  shared_ls: one lengthscale for all input dims (prssm.py:40)"""
+    g = {pre + 'zeta_pos': gz, pre + 'zeta_mean': gmu,
+         pre + 'zeta_var_unc': gs2 * torch.sigmoid(p[pre + 'zeta_var_unc']),
+         pre + 'variance_unc': (gvar * torch.sigmoid(p[pre + 'variance_unc'])).reshape(p[pre + 'variance_unc'].shape)}
+    lsu = p[pre + 'lengthscales_unc']
+    if shared_ls:
+        gls = gls.sum().reshape(lsu.shape)                   # its adjoint is the sum over the dims
+    g[pre + 'lengthscales_unc'] = gls * torch.sigmoid(lsu)
+    return g
+
+
 class HipElboGrad:
     """loss and d loss / d (12 unconstrained tensors) for one mini-batch on one device."""
 
@@ -318,12 +341,7 @@ class HipElboGrad:
                                                     # the contracted K^-1-adjoint images ride in the same buffer
 
     def _need_input_grads(self):
-        if self.f32:
-            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) exist for float64 engines only: the '
-                                      'float32 adjoint kernel keeps no data rows of the input adjoint')
-        if self.dist is not None:
-            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) are not available under a process '
-                                      'group: evaluate the shard on an engine without one')
+        need_input_grads(self.f32, self.dist)
 
     def _input_buffers(self, prob, ws):
         """per-chain buffers of the `_in` adjoints and the two results, kept with the workspace"""
@@ -364,7 +382,6 @@ class HipElboGrad:
 
     def _grads_finish(self, s):
         lib = _l.load()
-        dev = self.device
         st = _stream()
         ws, p, c, pflat, gB_f, gB_b, cL, cE = (s[k] for k in ('ws', 'p', 'c', 'pflat', 'gB_f', 'gB_b', 'cL', 'cE'))
         red = self.red
@@ -385,11 +402,16 @@ class HipElboGrad:
                                              _ptr(self.cflat), _ptr(self.tail_work), _ptr(self.gflat), st)
             _l.check(rc, 'cbfssm_train_tail_g_f64')
             grads = _flat_views(self.gflat, self.pl, self.dim_u)
-            if s.get('input_grads'):
-                grads['u'], grads['y'] = ws.grad_u, ws.grad_y
-            return loss, grads, terms
+        else:
+            grads = self._grads_tensor_library(p, c, red, tail, gB_f, gB_b)
+        if s.get('input_grads'):
+            grads['u'], grads['y'] = ws.grad_u, ws.grad_y
+        return loss, grads, terms
 
-        # ---- once-per-step adjoints and the chain through the positivity transforms (tensor-library restatement)
+    def _grads_tensor_library(self, p, c, red, tail, gB_f, gB_b):
+        """CBFSSM_TORCH_TAIL: the once-per-step adjoints and the chain through the positivity transforms, restated"""
+        dev = self.device
+        sf, sb = self.slab_f, self.slab_b
         grads = {}
         gvx = torch.zeros(self.dim_x, dtype=torch.float64, device=dev)
         gvy = torch.zeros(self.dim_x, dtype=torch.float64, device=dev)
@@ -399,21 +421,14 @@ class HipElboGrad:
                                        ('b', self.pack_b, red[sf:sf + sb], self.dob, gB_b)):
             gz, gmu, gs2, gvar, gls, small = _gp_adjoint(pack, slab, p[g + '.zeta_pos'], c[g + '.ls'], c[g + '.var'],
                                                          p[g + '.zeta_mean'], c[g + '.zvar'], Do, not self.stash, gBx)
-            grads[g + '.zeta_pos'] = gz
-            grads[g + '.zeta_mean'] = gmu
-            grads[g + '.zeta_var_unc'] = gs2 * torch.sigmoid(p[g + '.zeta_var_unc'])
-            grads[g + '.variance_unc'] = (gvar * torch.sigmoid(p[g + '.variance_unc'])).reshape(p[g + '.variance_unc'].shape)
-            grads[g + '.lengthscales_unc'] = gls * torch.sigmoid(p[g + '.lengthscales_unc'])
+            grads.update(gp_unc_grads(g + '.', p, gz, gmu, gs2, gvar, gls))
             gvx[:Do] += small[0:Do]
             if g == 'f':
                 gvy += small[16:16 + self.dim_x]
         gvy[:self.dim_y] += tail[3:]
         grads['var_x_unc'] = gvx * torch.sigmoid(p['var_x_unc'])
         grads['var_y_unc'] = gvy * torch.sigmoid(p['var_y_unc'])
-        if s.get('input_grads'):
-            grads['u'], grads['y'] = ws.grad_u, ws.grad_y
-
-        return loss, grads, terms
+        return grads
 
     # ---- chain-group split: chains never interact, so a pass can be issued in two pieces on two HIP streams.  When the
     # number of 16-chain groups is not a multiple of the CU count (C3: 320 groups on 256 CUs), the one-workgroup-per-

@@ -11,14 +11,15 @@ restatements below stay as cross-checks (CBFSSM_TORCH_GRU=1, CBFSSM_TORCH_CONV=1
 """
 import ctypes as C
 import os
-import math
+import types
 import torch
 
 from . import lib as _l
 from . import ops
 from .ops import _ptr, _stream, _f64, tf_forward, GPPack
 from .dist_utils import all_reduce_sum
-from .train import StashContract, FlatDict, _gp_adjoint, _timed, repacks_f32, repack_f32, g_mode, kgk_image
+from .train import (StashContract, FlatDict, _gp_adjoint, _timed, repacks_f32, repack_f32, g_mode, kgk_image,
+                    need_input_grads, gp_unc_grads)
 
 GP_NAMES = ('f.zeta_pos', 'f.zeta_mean', 'f.zeta_var_unc', 'f.variance_unc', 'f.lengthscales_unc')
 RECOG_NAMES = ('recog.gate_kernel', 'recog.gate_bias', 'recog.cand_kernel', 'recog.cand_bias', 'recog.dense_kernel',
@@ -68,6 +69,120 @@ def gru_recognition(recog, u, y, recog_len):
     return h @ recog['recog.dense_kernel'] + recog['recog.dense_bias']
 
 
+# ---- recognisers: x_0 of every sequence and, from d loss / d x_0, the gradients of the tensors they own.  An engine picks
+# one at construction and calls forward(params, p, u, y, keep, want_window) -> x0 (B, dim_x), contiguous and detached, then
+# backward(gx0_b, gwin, st) -> {name: gradient}; gwin: the (B, R, dim_u + dim_y) window adjoint to fill, or None.  What
+# backward needs stays on the object (one evaluation is in flight per engine, as for ops.TilePool).
+class OutputRecogniser:
+    """x_0 = [y_0, 0] (recog_model 'output'): no parameters, and the adjoint of x_0 goes to y_0 directly (half_input_grads
+    takes gx0 instead of a window adjoint)"""
+    names = ()
+
+    def __init__(self, n_hidden):
+        self.n_hidden = n_hidden
+
+    def forward(self, params, p, u, y, keep, want_window):
+        pad = torch.zeros(u.shape[0], self.n_hidden, dtype=u.dtype, device=u.device)
+        return torch.cat((y[:, 0, :], pad), dim=1).contiguous().detach()
+
+    def backward(self, gx0_b, gwin, st):
+        return {}
+
+
+# what tells the two fused recognition models apart: (tensor names, the param_elems symbol and whether it takes recog_len,
+# whether an activation buffer (cbfssm_gru_recog_act_elems) goes along, the forward / backward / backward `_in` symbols)
+KERNELS = {'gru': (RECOG_NAMES, 'cbfssm_gru_recog_param_elems', False, True,
+                   'cbfssm_gru_recog_f64', 'cbfssm_gru_recog_bwd_f64', 'cbfssm_gru_recog_bwd_in_f64'),
+           'conv': (CONV_NAMES, 'cbfssm_conv_recog_param_elems', True, False,
+                    'cbfssm_conv_recog_f32', 'cbfssm_conv_recog_bwd_f32', 'cbfssm_conv_recog_bwd_in_f32')}
+
+
+class KernelRecogniser:
+    """the GRU (float64) or the conv model (float32) as two launches, cbfssm_{gru,conv}_recog[_bwd[_in]]_*: one wave per
+    sequence, per-sequence gradient slabs reduced in fixed order into one vector that the returned gradients view"""
+
+    def __init__(self, kind, dims, recog_len, device):
+        self.names, self.elems, self.elems_R, self.has_act, *self.syms = KERNELS[kind]
+        self.fns = [getattr(_l.load(), s) for s in self.syms]                   # forward, backward, backward `_in`
+        self.dims, self.recog_len, self.device = dims, recog_len, device        # dims: (dim_u, dim_y, dim_x)
+        self._bufs = {}
+        self._held = None
+
+    def _flat(self, params, p):
+        """the recognition tensors (six of the GRU, four of the conv model) as one flat vector: the tail of the optimiser's own
+        storage when `params` are its views"""
+        names = self.names
+        flat = getattr(params, 'flat', None)
+        n = sum(p[k].numel() for k in names)
+        if flat is not None and flat.device == self.device and tuple(params.keys())[-len(names):] == names:
+            return flat[flat.numel() - n:]
+        return torch.cat([p[k].reshape(-1) for k in names])
+
+    def forward(self, params, p, u, y, keep, want_window):
+        lib = _l.load()
+        B, T = u.shape[0], u.shape[1]
+        R = min(self.recog_len, T)                           # (the window is the first recog_len steps: all of a shorter sequence)
+        rflat = self._flat(params, p)
+        if (B, R) not in self._bufs:
+            f = dict(dtype=torch.float64, device=self.device)
+            P = int(getattr(lib, self.elems)(*self.dims, *((R,) if self.elems_R else ())))
+            self._bufs[B, R] = types.SimpleNamespace(
+                P=P, x0=torch.zeros(B, self.dims[2], **f),
+                act=torch.zeros(int(lib.cbfssm_gru_recog_act_elems(B, R)), **f) if self.has_act else None,
+                gpart=torch.zeros((B + 32) * max(P, 0), **f))
+        b = self._bufs[B, R]
+        a = (B, T, *self.dims, R, _ptr(u), _ptr(y), _ptr(rflat))
+        if keep:    # (with the tensors behind the pointers: alive until backward, which lets go of them)
+            self._held = (b, a, (u, y, rflat), [(k, p[k].shape) for k in self.names])
+        act = (_ptr(b.act) if keep else None,) if self.has_act else ()
+        _l.check(self.fns[0](*a, _ptr(b.x0), *act, _stream()), self.syms[0])
+        return b.x0
+
+    def backward(self, gx0_b, gwin, st):
+        (b, a, _, shapes), self._held = self._held, None
+        a = a + ((_ptr(b.act),) if self.has_act else ()) + (_ptr(gx0_b.contiguous()), _ptr(b.gpart))
+        if gwin is not None:
+            _l.check(self.fns[2](*a, _ptr(gwin), st), self.syms[2])
+        else:
+            _l.check(self.fns[1](*a, st), self.syms[1])
+        rg = torch.zeros(b.P, dtype=torch.float64, device=self.device)
+        ops.reduce_partials(b.gpart, b.P, gx0_b.shape[0], rg, st)
+        grads, o = {}, 0
+        for k, shape in shapes:
+            grads[k] = rg[o:o + shape.numel()].view(shape)
+            o += shape.numel()
+        return grads
+
+
+class TorchRecogniser:
+    """gru_recognition / conv_recognition above through the tensor library's autograd: the cross-check of the kernels
+    (CBFSSM_TORCH_GRU=1, CBFSSM_TORCH_CONV=1) and the conv model at a recog_len beyond their limits"""
+
+    def __init__(self, names, recog_len):
+        self.names, self.recog_len = names, recog_len
+
+    def _fn(self):      # looked up in this module at every call: a test swaps the two functions to prove who runs them
+        return gru_recognition if self.names is RECOG_NAMES else conv_recognition
+
+    def forward(self, params, p, u, y, keep, want_window):
+        if not keep:
+            return self._fn()(p, u, y, self.recog_len).contiguous()
+        self.rp = {k: p[k].detach().clone().requires_grad_(True) for k in self.names}
+        self.win = ()
+        if want_window:         # the window's adjoint comes from the tensor library's autograd too
+            R = min(self.recog_len, u.shape[1])
+            self.win = tuple(t[:, :R].detach().clone().requires_grad_(True) for t in (u, y))
+        self.x0g = self._fn()(self.rp, *(self.win or (u, y)), self.recog_len)
+        return self.x0g.detach().contiguous()
+
+    def backward(self, gx0_b, gwin, st):
+        gl = torch.autograd.grad(self.x0g, [self.rp[k] for k in self.names] + list(self.win), grad_outputs=gx0_b)
+        self.x0g = self.rp = self.win = None
+        if gwin is not None:
+            gwin.copy_(torch.cat(gl[len(self.names):], dim=2))
+        return dict(zip(self.names, gl))
+
+
 class HipHalfGrad:
     """loss and gradients of CBFSSMHALF for one mini-batch on one device."""
 
@@ -114,16 +229,19 @@ class HipHalfGrad:
         self.fused_tail = self.slab_f > 0 and not os.environ.get('CBFSSM_TORCH_TAIL')
         self.gp_names = self.names[:7]                       # the five GP tensors, var_x_unc, var_y_unc: the tail's flat order
         self.tail_work = None
-        # the GRU recognition model as two launches (cbfssm_gru_recog[_bwd]_f64: one wave per sequence) instead of ~800 tensor-
-        # library launches through autograd; CBFSSM_TORCH_GRU=1 keeps the latter (same numbers, a cross-check)
+        # the recogniser: the GRU as two launches instead of ~800 tensor-library launches through autograd (CBFSSM_TORCH_GRU=1
+        # keeps the latter: same numbers, a cross-check); the conv model likewise (CBFSSM_TORCH_CONV=1), the tensor library
+        # also serving a recog_len beyond the kernels' limits (the library says where they are: param_elems < 0)
+        dims, R = (self.dim_u, self.dim_y, self.dim_x), int(config['recog_len'])
         self.fused_gru = self.rnn and not os.environ.get('CBFSSM_TORCH_GRU')
-        self._gru = {}
-        # the conv recognition model likewise (cbfssm_conv_recog[_bwd]_f32); CBFSSM_TORCH_CONV=1 keeps conv_recognition below,
-        # which also serves a recog_len beyond the kernels' limits (the library says where they are: param_elems < 0)
         self.fused_conv = (self.conv and not os.environ.get('CBFSSM_TORCH_CONV') and
-                           int(_l.load().cbfssm_conv_recog_param_elems(self.dim_u, self.dim_y, self.dim_x,
-                                                                       int(config['recog_len']))) >= 0)
-        self._conv = {}
+                           int(_l.load().cbfssm_conv_recog_param_elems(*dims, R)) >= 0)
+        if self.fused_gru or self.fused_conv:
+            self.recog = KernelRecogniser('gru' if self.rnn else 'conv', dims, R, self.device)
+        elif self.rnn or self.conv:
+            self.recog = TorchRecogniser(RECOG_NAMES if self.rnn else CONV_NAMES, R)
+        else:
+            self.recog = OutputRecogniser(self.dim_x - self.dim_y)
 
     def _problem(self, B, T, condition):
         c = self.config
@@ -131,74 +249,6 @@ class HipHalfGrad:
             return _l.make_problem(B, self.S, T, self.dim_x, self.dim_u, self.dim_y, self.M, 1, 1.0, False, half=True)
         return _l.make_problem(B, self.S, T, self.dim_x, self.dim_u, self.dim_y, self.M, c['recog_len'], c['k_factor'],
                                condition, half=True)
-
-    def _recog_params(self, p):
-        if self.rnn:
-            return RECOG_NAMES
-        return CONV_NAMES if self.conv else ()
-
-    def _recog(self, rp, u, y):
-        if self.rnn:
-            return gru_recognition(rp, u, y, self.config['recog_len'])
-        return conv_recognition(rp, u, y, self.config['recog_len'])
-
-    def _recog_flat(self, params, p):
-        """the recognition tensors (six of the GRU, four of the conv model) as one flat vector: the tail of the optimiser's own
-        storage when `params` are its views"""
-        names = self._recog_params(p)
-        flat = getattr(params, 'flat', None)
-        n = sum(p[k].numel() for k in names)
-        if flat is not None and flat.device == self.device and tuple(params.keys())[-len(names):] == names:
-            return flat[flat.numel() - n:]
-        return torch.cat([p[k].reshape(-1) for k in names])
-
-    def _gru_forward(self, rflat, u, y, keep):
-        lib = _l.load()
-        B, T = u.shape[0], u.shape[1]
-        R = min(int(self.config['recog_len']), T)            # (the window is the first recog_len steps: all of a shorter sequence)
-        f = dict(dtype=torch.float64, device=self.device)
-        key = (B, R)
-        if key not in self._gru:
-            P = int(lib.cbfssm_gru_recog_param_elems(self.dim_u, self.dim_y, self.dim_x))
-            self._gru[key] = {'x0': torch.zeros(B, self.dim_x, **f), 'P': P,
-                              'act': torch.zeros(int(lib.cbfssm_gru_recog_act_elems(B, R)), **f),
-                              'gpart': torch.zeros((B + 32) * P, **f)}
-        g = self._gru[key]
-        rc = lib.cbfssm_gru_recog_f64(B, T, self.dim_u, self.dim_y, self.dim_x, R, _ptr(u), _ptr(y), _ptr(rflat), _ptr(g['x0']),
-                                      _ptr(g['act']) if keep else None, _stream())
-        _l.check(rc, 'cbfssm_gru_recog_f64')
-        return g
-
-    def _conv_forward(self, rflat, u, y):
-        lib = _l.load()
-        B, T = u.shape[0], u.shape[1]
-        R = min(int(self.config['recog_len']), T)
-        key = (B, R)
-        if key not in self._conv:
-            f = dict(dtype=torch.float64, device=self.device)
-            P = int(lib.cbfssm_conv_recog_param_elems(self.dim_u, self.dim_y, self.dim_x, R))
-            self._conv[key] = {'x0': torch.zeros(B, self.dim_x, **f), 'P': P, 'R': R,
-                               'gpart': torch.zeros((B + 32) * max(P, 0), **f)}
-        g = self._conv[key]
-        rc = lib.cbfssm_conv_recog_f32(B, T, self.dim_u, self.dim_y, self.dim_x, R, _ptr(u), _ptr(y), _ptr(rflat), _ptr(g['x0']),
-                                       _stream())
-        _l.check(rc, 'cbfssm_conv_recog_f32')
-        return g
-
-    def _x0(self, p, u, y, params=None):
-        if self.fused_gru:
-            return self._gru_forward(self._recog_flat(params, p), u, y, keep=False)['x0']
-        if self.fused_conv:
-            return self._conv_forward(self._recog_flat(params, p), u, y)['x0']
-        if self.rnn or self.conv:
-            return self._recog(p, u, y)
-        B = u.shape[0]
-        return torch.cat((y[:, 0, :], torch.zeros(B, self.dim_x - self.dim_y, dtype=u.dtype, device=u.device)), dim=1)
-
-    def _loops(self, prob, ws, c, u, y, x0, eps_f):
-        """the time-loop entry points bound to this evaluation's operands"""
-        return ops.TimeLoops(prob, ws, self.pack_f, None, c['var_x'], c['var_y'], u, y, eps_f, x0=x0, cL=self.cL,
-                             f32=self.f32)
 
     def _forward(self, lp, p, c):
         st = _stream()
@@ -226,10 +276,7 @@ class HipHalfGrad:
             lib = _l.load()
             f = dict(dtype=torch.float64, device=self.device)
             N = prob.B * prob.S
-
-            class WS:
-                pass
-            ws = WS()
+            ws = types.SimpleNamespace()
             ws.n_kl = int(lib.cbfssm_forward_pass_partials(C.byref(prob)))
             ws.n_f = int(lib.cbfssm_rev_workgroups(C.byref(prob), 0))
             ws.x = torch.zeros(prob.T, N, prob.dim_x, **f)
@@ -269,17 +316,32 @@ class HipHalfGrad:
         z = torch.zeros((), dtype=torch.float64, device=self.device)
         return loss, {'loglik': loglik, 'kl_x': kl_x, 'entropy': z, 'kl_z_f': out[3], 'kl_z_b': z, 'info': out[7]}
 
-    def forward(self, params, u, y, noise, condition=True, weight=1.0, local=False):
+    def _evaluate(self, params, u, y, noise, condition, grad=False, input_grads=False):
+        """what forward() and loss_and_grads() share: the casts, the problem and its workspace, the constrained parameters, x_0
+        from the recogniser and the forward evaluation.  Returns (p, c, lp): lp the time-loop entry points bound to all of it.
+        grad: the recogniser and the pass keep what their adjoints need."""
         dev = self.device
         p = {k: _f64(params[k], dev) for k in self.names}
         u, y = _f64(u, dev), _f64(y, dev)
         prob = self._problem(u.shape[0], u.shape[1], condition)
-        ws = self._workspace(prob)
-        with torch.no_grad():
-            x0 = self._x0(p, u, y, params).contiguous()
+        self.last_ws = ws = self._workspace(prob)
+        # (forward() has always evaluated the recogniser ahead of the transforms, loss_and_grads() behind them: kept, so that
+        # either issues the launches it always did, in their order)
+        if not grad:
+            with torch.no_grad():
+                x0 = self.recog.forward(params, p, u, y, False, False)
         c = self._constrained(p)
-        self._forward(self._loops(prob, ws, c, u, y, x0, _f64(noise['eps_f'], dev)), p, c)
-        self.last_ws = ws
+        eps_f = _f64(noise['eps_f'], dev)
+        if grad:
+            x0 = self.recog.forward(params, p, u, y, True, input_grads)
+        lp = ops.TimeLoops(prob, ws, self.pack_f, None, c['var_x'], c['var_y'], u, y, eps_f, x0=x0, cL=self.cL, f32=self.f32)
+        if input_grads:
+            lp.in_bufs = self._input_buffers(prob, ws)
+        self._forward(lp, p, c)
+        return p, c, lp
+
+    def forward(self, params, u, y, noise, condition=True, weight=1.0, local=False):
+        ws = self._evaluate(params, u, y, noise, condition)[2].ws
         red2 = None
         if self.dist is not None and not local:
             red2 = ws.out[0:2].clone()
@@ -290,14 +352,13 @@ class HipHalfGrad:
         return loss, terms, ws
 
     def _need_input_grads(self):
-        if self.f32:
-            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) exist for float64 engines only: the '
-                                      'float32 adjoint kernel keeps no data rows of the input adjoint')
-        if self.dist is not None:
-            raise NotImplementedError('input gradients (d loss / d u, d loss / d y) are not available under a process '
-                                      'group: evaluate the shard on an engine without one')
+        need_input_grads(self.f32, self.dist)
 
-    def _input_buffers(self, prob, ws, R):
+    def _window(self, T):
+        """rows of u, y that the recognition model reads"""
+        return min(int(self.config['recog_len']), T)
+
+    def _input_buffers(self, prob, ws):
         """per-chain buffers of the `_in` adjoint (gin_f, -, gyo), the window adjoint and the two results, kept with the
         workspace"""
         if getattr(ws, 'in_bufs', None) is None:
@@ -306,63 +367,19 @@ class HipHalfGrad:
             n_f, n_o = (int(fn(C.byref(prob))) for fn in (lib.cbfssm_input_adjoint_fwd_elems, lib.cbfssm_input_adjoint_obs_elems))
             assert min(n_f, n_o) >= 0, (n_f, n_o)
             ws.in_bufs = (torch.zeros(max(n_f, 1), **f), None, torch.zeros(max(n_o, 1), **f))
-            ws.gwin = torch.zeros(prob.B, R, prob.dim_u + prob.dim_y, **f)
+            ws.gwin = torch.zeros(prob.B, self._window(prob.T), prob.dim_u + prob.dim_y, **f)
             ws.grad_u = torch.zeros(prob.B, prob.T, prob.dim_u, **f)
             ws.grad_y = torch.zeros(prob.B, prob.T, prob.dim_y, **f)
         return ws.in_bufs
 
-    def loss_and_grads(self, params, u, y, noise, condition=True, weight=1.0, local=False, input_grads=False):
-        """input_grads: the grads also hold 'u' (B,T,dim_u) and 'y' (B,T,dim_y), the gradient of the loss with respect to the
-        input and output sequences (tf.gradients(loss, sample_in / sample_out)): through the time loop, the log-likelihood
-        and the recognition model's window.  float64 engines without a process group only; an eager path (HipHalfTrainStep
-        never takes it)."""
-        if input_grads:
-            self._need_input_grads()
-        lib = _l.load()
-        dev = self.device
-        p = {k: _f64(params[k], dev) for k in self.names}
-        u, y = _f64(u, dev), _f64(y, dev)
-        B, T = u.shape[0], u.shape[1]
-        prob = self._problem(B, T, condition)
-        ws = self._workspace(prob)
-        self.last_ws = ws
-        c = self._constrained(p)
-        eps_f = _f64(noise['eps_f'], dev)
-        rp = {}
-        rnames = self._recog_params(p)
-        gru = conv = None
-        R = min(int(self.config['recog_len']), T)
-        win = ()
-        if self.fused_gru:
-            rflat = self._recog_flat(params, p)
-            gru = self._gru_forward(rflat, u, y, keep=True)
-            x0 = gru['x0']
-        elif self.fused_conv:
-            rflat = self._recog_flat(params, p)
-            conv = self._conv_forward(rflat, u, y)
-            x0 = conv['x0']
-        elif rnames:
-            rp = {k: p[k].detach().clone().requires_grad_(True) for k in rnames}
-            if input_grads:     # the window's adjoint comes from the tensor library's autograd too
-                win = tuple(t[:, :R].detach().clone().requires_grad_(True) for t in (u, y))
-            x0g = self._recog(rp, *(win or (u, y)))
-            x0 = x0g.detach().contiguous()
-        else:
-            x0 = self._x0(p, u, y).contiguous()
-        lp = self._loops(prob, ws, c, u, y, x0, eps_f)
-        if input_grads:
-            lp.in_bufs = self._input_buffers(prob, ws, R)
-        self._forward(lp, p, c)
-
-        st = _stream()
-        pb = C.byref(prob)
-        sf = self.slab_f
-        red = ws.red
-        lay = C.byref(self.pack_f.layout)
-        groups = (B * self.S + 15) // 16
-        gB = None
-        prof = getattr(self, '_prof', None)
+    def _adjoint(self, lp, ws, prof, st):
+        """the adjoint of the time loop, its per-workgroup slabs reduced into ws.red[:slab_f].  Returns the image of
+        d loss / d K^-1 that goes beside the slab (stash tile heights), or None."""
+        prob, sf, red, dev = lp.prob, self.slab_f, ws.red, self.device
         if self.stash and not self.f32:
+            # float64 at M > 112: time-chunked launches that fit the stash, each followed by its reduction and the GEMM that
+            # contracts the stashed A2bar / K tiles into the image (the forward-pass half of HipElboGrad._adjoint_stash)
+            groups = (prob.B * self.S + 15) // 16
             Mp = self.pack_f.layout.Mp
             cols_max = max(groups * 16, self.stash_bytes // (2 * Mp * 8))
             f = dict(dtype=torch.float64, device=dev)
@@ -372,11 +389,10 @@ class HipHalfGrad:
             if getattr(self, '_contract', None) is None:
                 self._contract = StashContract(self.pack_f, dev)
             self._contract.image.zero_()
-            gB = self._contract.image
             tmp = torch.zeros(sf, **f)
             red[:sf].zero_()
             per = max(1, cols_max // (groups * 16))
-            t_hi = T - 2
+            t_hi = prob.T - 2
             while True:
                 t_lo = max(0, t_hi - per + 1)
                 cols = groups * max(0, t_hi - t_lo + 1) * 16
@@ -388,75 +404,38 @@ class HipHalfGrad:
                     _timed(prof, 'stash_contraction', None, lambda: self._contract.add(sa, sk, cols, st))
                 t_hi = t_lo - 1
                 if t_hi < 0:
-                    break
-        else:
-            # one launch for the whole time loop (float32: at every tile height, into the non-stash slab)
-            _timed(prof, 'forward_pass_adjoint', None, lambda: lp.half_forward_pass_bwd(prob, st))
-            if not self.repack32:
-                assert not self.f32 or self.slab32_f == sf
-                ops.reduce_partials(ws.gpart_f, sf, ws.n_f, red[:sf], st)
-            else:
-                s32, nb = self.slab32_f, self.pack_f.layout.NBLK
-                if self._tmp32 is None:
-                    self._tmp32 = torch.zeros(s32 + nb * nb * 256, dtype=torch.float64, device=dev)
-                t32, gB = self._tmp32[:s32], self._tmp32[s32:]
-                ops.reduce_partials(ws.gpart_f, s32, ws.n_f, t32, st)
-                repack_f32(t32, red[:sf], gB, nb)
+                    return self._contract.image
+        # one launch for the whole time loop (float32: at every tile height, into the non-stash slab)
+        _timed(prof, 'forward_pass_adjoint', None, lambda: lp.half_forward_pass_bwd(prob, st))
+        if not self.repack32:
+            assert not self.f32 or self.slab32_f == sf
+            ops.reduce_partials(ws.gpart_f, sf, ws.n_f, red[:sf], st)
+            return None
+        s32, nb = self.slab32_f, self.pack_f.layout.NBLK
+        if self._tmp32 is None:
+            self._tmp32 = torch.zeros(s32 + nb * nb * 256, dtype=torch.float64, device=dev)
+        t32, gB = self._tmp32[:s32], self._tmp32[s32:]
+        ops.reduce_partials(ws.gpart_f, s32, ws.n_f, t32, st)
+        repack_f32(t32, red[:sf], gB, nb)
+        return gB
 
-        # data scalars and the log-likelihood's pull on var_y (cbfssmhalf.py:181-189): tail = [loglik, kl_x, 0, d/d var_y]
-        tail = red[sf:]
-        _l.check(lib.cbfssm_data_tail_f64(pb, _ptr(c['var_y']), _ptr(ws.ll_part), _ptr(ws.out), self.cL, _ptr(tail), st),
-                 'cbfssm_data_tail_f64')
-        gx0_b = ws.gx0.view(B, self.S, self.dim_x).sum(1)        # d loss / d x_0 per sequence (tiled over S, :87)
-        rgrads = {}
-        gwin = ws.gwin if input_grads and rnames else None
-        if gru is not None or conv is not None:
-            if gru is not None:
-                P, gpart = gru['P'], gru['gpart']
-                a = (B, T, self.dim_u, self.dim_y, self.dim_x, R, _ptr(u), _ptr(y), _ptr(rflat), _ptr(gru['act']),
-                     _ptr(gx0_b.contiguous()), _ptr(gpart))
-                if input_grads:
-                    _l.check(lib.cbfssm_gru_recog_bwd_in_f64(*a, _ptr(gwin), st), 'cbfssm_gru_recog_bwd_in_f64')
-                else:
-                    _l.check(lib.cbfssm_gru_recog_bwd_f64(*a, st), 'cbfssm_gru_recog_bwd_f64')
-            else:
-                P, gpart = conv['P'], conv['gpart']
-                a = (B, T, self.dim_u, self.dim_y, self.dim_x, conv['R'], _ptr(u), _ptr(y), _ptr(rflat),
-                     _ptr(gx0_b.contiguous()), _ptr(gpart))
-                if input_grads:
-                    _l.check(lib.cbfssm_conv_recog_bwd_in_f32(*a, _ptr(gwin), st), 'cbfssm_conv_recog_bwd_in_f32')
-                else:
-                    _l.check(lib.cbfssm_conv_recog_bwd_f32(*a, st), 'cbfssm_conv_recog_bwd_f32')
-            rg = torch.zeros(P, dtype=torch.float64, device=dev)
-            ops.reduce_partials(gpart, P, B, rg, st)
-            o = 0
-            for k in rnames:
-                rgrads[k] = rg[o:o + p[k].numel()].view(p[k].shape)
-                o += p[k].numel()
-        elif rnames:
-            gl = torch.autograd.grad(x0g, [rp[k] for k in rnames] + list(win), grad_outputs=gx0_b)
-            rgrads = dict(zip(rnames, gl))
-            if input_grads:
-                gwin.copy_(torch.cat(gl[len(rnames):], dim=2))
-        if input_grads:
-            # x_0 = [y_0, 0] without a recognition model: its adjoint goes to y_0 directly
-            lp.half_input_grads(None if rnames else ws.gx0, gwin, R, ws.grad_u, ws.grad_y, st)
-        if self.dist is not None and not local:
-            # one flat buffer per step: [slab | data scalars | stash-mode K^-1-adjoint image | recognition-model gradients]
-            pieces = [red] + ([gB] if gB is not None else []) + [rgrads[k].reshape(-1) for k in rnames]
-            flat = torch.cat([t.reshape(-1) for t in pieces])
-            if weight != 1.0:
-                flat.mul_(float(weight))
-            all_reduce_sum(flat, self.dist)
-            o = 0
-            for t in pieces:
-                t.copy_(flat[o:o + t.numel()].view_as(t))
-                o += t.numel()
+    def _all_reduce(self, pieces, weight):
+        """the ONE collective of a step, over one flat buffer of the pieces, which take their sums back"""
+        flat = torch.cat([t.reshape(-1) for t in pieces])
+        if weight != 1.0:
+            flat.mul_(float(weight))
+        all_reduce_sum(flat, self.dist)
+        o = 0
+        for t in pieces:
+            t.copy_(flat[o:o + t.numel()].view_as(t))
+            o += t.numel()
 
-        pre = self.pre
-        loss, terms = self._terms(ws, tail[0:2])
+    def _param_grads(self, params, p, c, red, gB, rgrads, st):
+        """from the reduced slab (and image) to the gradients of the unconstrained tensors; the recogniser's ride along"""
+        lib, dev, pre, sf = _l.load(), self.device, self.pre, self.slab_f
         if self.fused_tail:
             # the K_mm -> Cholesky -> K^-1 adjoint, the prior KL and the chain through the positivity transforms in HIP
+            lay = C.byref(self.pack_f.layout)
             gp = [p[k].reshape(-1) for k in self.gp_names]
             pflat = getattr(params, 'flat', None)
             ngp = sum(t.numel() for t in gp)
@@ -467,7 +446,7 @@ class HipHalfGrad:
             if self.tail_work is None:
                 nw = int(lib.cbfssm_train_tail_half_work_elems(lay))
                 self.tail_work = torch.zeros(nw, dtype=torch.float64, device=dev)
-            gall = torch.zeros(ngp + sum(rgrads[k].numel() for k in rnames), dtype=torch.float64, device=dev)
+            gall = torch.zeros(ngp + sum(g.numel() for g in rgrads.values()), dtype=torch.float64, device=dev)
             rc = lib.cbfssm_train_tail_half_f64(lay, _ptr(self.pack_f.buf), _ptr(self.pack_kl.buf) if self.pack_kl is not None else None,
                                                 int(lsc.numel() == 1), _ptr(red), _ptr(gB), 0, g_mode(self.f32, self.pack_f.layout), self.dim_y, _ptr(pflat), _ptr(cflat),
                                                 _ptr(self.tail_work), _ptr(gall), st)
@@ -478,30 +457,47 @@ class HipHalfGrad:
             for k in self.gp_names:
                 grads[k] = gall[o:o + p[k].numel()].view(p[k].shape)
                 o += p[k].numel()
-            for k in rnames:
-                gall[o:o + rgrads[k].numel()] = rgrads[k].reshape(-1)
-                grads[k] = gall[o:o + rgrads[k].numel()].view(rgrads[k].shape)
-                o += rgrads[k].numel()
-            if input_grads:
-                grads['u'], grads['y'] = ws.grad_u, ws.grad_y
-            return loss, grads, terms
-
+            for k, g in rgrads.items():
+                gall[o:o + g.numel()] = g.reshape(-1)
+                grads[k] = gall[o:o + g.numel()].view(g.shape)
+                o += g.numel()
+            return grads
         grads = dict(rgrads)
         if self.f32:
             gB = kgk_image(self.pack_f, red[:sf], gB)
         gz, gmu, gs2, gvar, gls, small = _gp_adjoint(self.pack_f, red[:sf], p[pre + 'zeta_pos'], c['ls'], c['var'],
                                                      p[pre + 'zeta_mean'], c['zvar'], self.dim_x, not self.stash, gB,
                                                      self.pack_kl)
-        grads[pre + 'zeta_pos'] = gz
-        grads[pre + 'zeta_mean'] = gmu
-        grads[pre + 'zeta_var_unc'] = gs2 * torch.sigmoid(p[pre + 'zeta_var_unc'])
-        grads[pre + 'variance_unc'] = (gvar * torch.sigmoid(p[pre + 'variance_unc'])).reshape(p[pre + 'variance_unc'].shape)
-        lsu = p[pre + 'lengthscales_unc']
-        if lsu.numel() == 1:
-            gls = gls.sum().reshape(lsu.shape)               # shared lengthscale: its adjoint is the sum over the dims
-        grads[pre + 'lengthscales_unc'] = gls * torch.sigmoid(lsu)
+        grads.update(gp_unc_grads(pre, p, gz, gmu, gs2, gvar, gls, shared_ls=p[pre + 'lengthscales_unc'].numel() == 1))
         grads['var_x_unc'] = small[0:self.dim_x] * torch.sigmoid(p['var_x_unc'])
-        grads['var_y_unc'] = (small[16:16 + self.dim_y] + tail[3:]) * torch.sigmoid(p['var_y_unc'])
+        grads['var_y_unc'] = (small[16:16 + self.dim_y] + red[sf + 3:]) * torch.sigmoid(p['var_y_unc'])
+        return grads
+
+    def loss_and_grads(self, params, u, y, noise, condition=True, weight=1.0, local=False, input_grads=False):
+        """input_grads: the grads also hold 'u' (B,T,dim_u) and 'y' (B,T,dim_y), the gradient of the loss with respect to the
+        input and output sequences (tf.gradients(loss, sample_in / sample_out)): through the time loop, the log-likelihood
+        and the recognition model's window.  float64 engines without a process group only; an eager path (HipHalfTrainStep
+        never takes it)."""
+        if input_grads:
+            self._need_input_grads()
+        p, c, lp = self._evaluate(params, u, y, noise, condition, grad=True, input_grads=input_grads)
+        prob, ws, st, rec = lp.prob, lp.ws, _stream(), self.recog
+        gB = self._adjoint(lp, ws, getattr(self, '_prof', None), st)
+        # data scalars and the log-likelihood's pull on var_y (cbfssmhalf.py:181-189): tail = [loglik, kl_x, 0, d/d var_y]
+        tail = ws.red[self.slab_f:]
+        _l.check(_l.load().cbfssm_data_tail_f64(C.byref(prob), _ptr(c['var_y']), _ptr(ws.ll_part), _ptr(ws.out), self.cL,
+                                                _ptr(tail), st), 'cbfssm_data_tail_f64')
+        gx0_b = ws.gx0.view(prob.B, self.S, self.dim_x).sum(1)   # d loss / d x_0 per sequence (tiled over S, :87)
+        gwin = ws.gwin if input_grads and rec.names else None
+        rgrads = rec.backward(gx0_b, gwin, st)
+        if input_grads:
+            # x_0 = [y_0, 0] without a recognition model: its adjoint goes to y_0 directly
+            lp.half_input_grads(None if rec.names else ws.gx0, gwin, self._window(prob.T), ws.grad_u, ws.grad_y, st)
+        if self.dist is not None and not local:
+            # [slab | data scalars | stash-mode K^-1-adjoint image | recognition-model gradients]
+            self._all_reduce([ws.red] + ([gB] if gB is not None else []) + [rgrads[k].reshape(-1) for k in rec.names], weight)
+        loss, terms = self._terms(ws, tail[0:2])
+        grads = self._param_grads(params, p, c, ws.red, gB, rgrads, st)
         if input_grads:
             grads['u'], grads['y'] = ws.grad_u, ws.grad_y
         return loss, grads, terms
