@@ -88,8 +88,10 @@ def window_flags(t, R, run):
     return (t + R + 1) % (2 * R) == 0, t % (2 * R) >= R
 
 
-def elbo_step(config, params, u, y, noise, condition=True, want_pred=False):
-    """cbfssm/model/cbfssm.py:25-271.  params / u / y / noise: float64 torch tensors (params may require grad)."""
+def elbo_step(config, params, u, y, noise, condition=True, want_pred=False, u_b=None, y_b=None):
+    """cbfssm/model/cbfssm.py:25-271.  params / u / y / noise: float64 torch tensors (params may require grad).
+    u_b / y_b: test hook -- when given, the two backward runs build their GP input (:137) from these tensors instead of
+    u / y (same values, other leaves: autograd then separates the paths of DESIGN 3.2a); None: the reference's graph."""
     dim_u, dim_y, dim_x = config['ds'].dim_u, config['ds'].dim_y, config['dim_x']
     S, R, k_factor = config['samples'], config['recog_len'], config['k_factor']
     lf = config['loss_factors']
@@ -103,6 +105,8 @@ def elbo_step(config, params, u, y, noise, condition=True, want_pred=False):
 
     u_dub = u.permute(1, 0, 2)[:, :, None, :].repeat(1, 1, S, 1)                         # :74-76 (physical tile)
     y_dub = y.permute(1, 0, 2)[:, :, None, :].repeat(1, 1, S, 1)                         # :80-82
+    u_dub_b = u_dub if u_b is None else u_b.permute(1, 0, 2)[:, :, None, :].repeat(1, 1, S, 1)
+    y_dub_b = y_dub if y_b is None else y_b.permute(1, 0, 2)[:, :, None, :].repeat(1, 1, S, 1)
 
     # ---- backward, two runs (cbfssm.py:84-158)
     y2 = [None] * T
@@ -113,7 +117,7 @@ def elbo_step(config, params, u, y, noise, condition=True, want_pred=False):
         for t in range(T - 1, -1, -1):
             resample, write = window_flags(t, R, run)
             hidden = noise['hid_b'][run, t][:, :, None].repeat(1, 1, dim_out) if resample else h   # :133-136
-            in_t = torch.cat((hidden, u_dub[t], y_dub[t]), dim=2)                        # :137
+            in_t = torch.cat((hidden, u_dub_b[t], y_dub_b[t]), dim=2)                    # :137
             fmean, fvar = gp_b.predict(in_t.reshape(B * S, dim_x + dim_u))               # :140-141
             fmean = fmean.reshape(B, S, dim_out) + in_t[:, :, :dim_out]                  # :143-145
             fvar = fvar.reshape(B, S, dim_out) + var_x[:dim_out]                         # :144-146

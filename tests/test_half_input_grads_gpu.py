@@ -49,8 +49,15 @@ def _conv_rule(tag, g, g_ref, g_truth):
 def _judge_engine(name, cond, cfg, w, loss, grads, tag=''):
     """loss, parameter gradients, d loss / d u and d loss / d y of one engine call against the oracle of the case"""
     variant, recog = hc.CASES[name][:2]
-    conv = recog == 'conv'
-    loss_ref, gref, gu_ref, gy_ref = hc.oracle(name, cond)
+    truth = hc.oracle(name, cond, True) if recog == 'conv' else None
+    _judge_reference(name, variant, hc.oracle(name, cond), cond, cfg, w, loss, grads, tag=tag, truth=truth)
+
+
+def _judge_reference(name, variant, ref, cond, cfg, w, loss, grads, tag='', truth=None):
+    """the same against a reference handed in (half_input_grads_cases.oracle_run of any set-up: the tile-grid rows of
+    tests/test_input_grads_tile_grid_gpu.py); truth: the reference with the conv recogniser in float64, conv cases only"""
+    conv = truth is not None
+    loss_ref, gref, gu_ref, gy_ref = ref
     hc.assert_reference_structure(name, cfg, gu_ref, gy_ref)
     gu, gy = grads['u'].cpu().numpy(), grads['y'].cpu().numpy()
     assert gu.shape == gu_ref.shape and gy.shape == gy_ref.shape
@@ -72,7 +79,7 @@ def _judge_engine(name, cond, cfg, w, loss, grads, tag=''):
     if w.T - 1 >= R and w.dim_u:
         assert not gu[:, w.T - 1].any(), 'd loss / d u must be exactly zero at t = T - 1: the last input feeds nothing'
     if conv:
-        _, _, gu_t, gy_t = hc.oracle(name, cond, True)
+        _, _, gu_t, gy_t = truth
         _conv_rule(tag + 'u window rows', gu[:, :R], gu_ref[:, :R], gu_t[:, :R])
         _conv_rule(tag + 'y window rows', gy[:, :R], gy_ref[:, :R], gy_t[:, :R])
         within_rule(tag + 'u rows t>=R', gu[:, R:w.T - 1], gu_ref[:, R:w.T - 1])

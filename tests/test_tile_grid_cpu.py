@@ -31,8 +31,9 @@ def _nblk(name):
 
 
 def test_launcher_families_list_the_same_leaves():
-    """float64 passes, float64 adjoint, float32 passes, float32 adjoint: one tree, four times"""
+    """float64 passes, float64 adjoint, float64 input-gradient adjoint, float32 passes, float32 adjoint: one tree, five times"""
     fam = tg.compiled_families()
+    assert set(fam) == {'pass', 'rev', 'revin', 'pass32', 'rev32'}
     heights, dks = fam['pass']
     assert len(heights) >= 8 and {dk for dk, _ in dks} >= {2, 4, 6} and {md for _, md in dks} == {'fwd', 'bwd'}
     for key, (h, d) in fam.items():
@@ -99,6 +100,89 @@ def test_both_sides_of_the_adjoints_lds_switch_at_seven_row_blocks():
         assert False in sides or forced, dk
     assert tg.kinv_in_lds(7, 2, 108) and not tg.kinv_in_lds(7, 2, 109)
     assert tg.kinv_in_lds(7, 4, 112) and tg.kinv_in_lds(7, 6, 112)
+
+
+def _today_kinv_in_lds(nblk, dk, M):
+    """kinv_in_lds as it stood before it took `ig` (RevInGeom<DK, false>), kept to pin the default"""
+    rb = 2 if nblk > 7 else 1
+    waves = (nblk + rb - 1) // rb
+    jb = (4 * dk + 1 + 15) // 16
+    psl, ecs = (272, 16) if jb == 2 else (max(jb, 2) * 256, 0)
+    base = 2 * 4 * dk * 17 + 2 * (16 * nblk) * 17 + 2 * 16 * 17 + waves * psl + 64 + waves * ecs
+    return base + nblk * ((M + 3) // 4) * 64 <= 163840 // 8
+
+
+def _height_range(nb):
+    return range(16 * ([0] + HEIGHTS)[HEIGHTS.index(nb)] + 1, 16 * nb + 1)
+
+
+def test_lds_switch_default_is_unchanged_and_the_input_gradient_geometry_differs_where_splitj_was_on():
+    for nb in HEIGHTS:
+        for dk in (2, 4, 6):
+            for M in range(1, 16 * nb + 1):
+                assert tg.kinv_in_lds(nb, dk, M) == tg.kinv_in_lds(nb, dk, M, ig=False) == _today_kinv_in_lds(nb, dk, M)
+                if dk == 2:         # JB = 1: one 16-row block of input rows, nothing to split, IG changes nothing
+                    assert tg.kinv_in_lds(nb, dk, M, ig=True) == tg.kinv_in_lds(nb, dk, M), (nb, dk, M)
+    # DK 4, 6 (JB = 2) without SPLITJ: 7 * (512 - 272 - 16) more doubles of partial tiles at seven row blocks, and the
+    # image that fits at every M of the height by default leaves the LDS after M = 104
+    for dk in (4, 6):
+        assert tg.kinv_in_lds(7, dk, 104, ig=True) and not tg.kinv_in_lds(7, dk, 105, ig=True) and tg.kinv_in_lds(7, dk, 112)
+
+
+def test_every_leaf_of_the_input_gradient_family_is_reached():
+    """launch_revin_n: 8 heights x 3 DK x 2 directions, each in two K^-1 placements = 96 kernels.  The BLDS = true
+    kernels of the heights >= 10 cannot be launched (the image never fits next to the tiles); the grid reaches every
+    other one: the rows by shape, the streamed kernels of heights 1, 2, 4 through IG_NO_BLDS_CASES."""
+    heights, dks = tg.compiled_families()['revin']
+    leaves = {(nb, dk, mode) for nb in heights for dk, mode in dks}
+    assert len(leaves) == 48 and leaves <= tg.compiled_leaves()
+    got = {key[:3] for _, kw in tg.CASES for key in tg.revin_leaf_keys(kw)}
+    missing = sorted(leaves - got)
+    assert not missing, 'no row of tile_grid.CASES reaches (NBLK, DK, mode) %s of the input-gradient family' % (missing,)
+    launchable = {(nb, dk, mode, blds) for nb, dk, mode in leaves for blds in (False, True)
+                  if not blds or any(tg.kinv_in_lds(nb, dk, M, ig=True) for M in _height_range(nb))}
+    never = {(nb, dk, mode, True) for nb, dk, mode in leaves if nb >= 10}
+    assert len(launchable) == 72 and launchable == {(nb, dk, mode, b) for nb, dk, mode in leaves for b in (False, True)} - never
+    reached = {key for _, kw in tg.CASES for key in tg.revin_leaf_keys(kw)}
+    reached |= {key for n in tg.IG_NO_BLDS_CASES for key in tg.revin_leaf_keys(tg.CASE_KW[n], no_blds=True)}
+    assert reached == launchable, sorted(launchable - reached)
+
+
+def test_input_gradient_family_both_placements_at_seven_row_blocks_by_shape():
+    seven = [(name, kw) for name, kw in tg.CASES if 64 < kw['M'] <= 112]
+    for dk in (2, 4, 6):
+        for mode in ('fwd', 'bwd'):
+            sides = {blds for _, kw in seven for nb, k, md, blds in tg.revin_leaf_keys(kw) if (nb, k, md) == (7, dk, mode)}
+            assert sides == {True, False}, (dk, mode, sides)
+    # the hand-checked table of the rows: (DK, M in LDS, M streamed)
+    for dk, lds, streamed in ((6, (65, 97, 103), (106, 112)), (4, (80,), (105,)), (2, (96, 100, 101, 108), (109,))):
+        Ms = {kw['M'] for _, kw in seven if tg.input_steps(tg.workload(kw).D) == dk}
+        assert Ms == set(lds) | set(streamed), (dk, sorted(Ms))
+        assert all(tg.kinv_in_lds(7, dk, M, ig=True) for M in lds) and not any(tg.kinv_in_lds(7, dk, M, ig=True) for M in streamed)
+    # the thresholds themselves: M = 108 | 109 at DK 2, 104 | 105 at DK 4 and 6
+    for dk, last in ((2, 108), (4, 104), (6, 104)):
+        assert [M for M in _height_range(7) if tg.kinv_in_lds(7, dk, M, ig=True)] == list(range(65, last + 1)), dk
+
+
+def test_input_gradient_family_placement_is_fixed_at_the_other_heights():
+    """always LDS at heights 1, 2, 4; never at heights >= 10 -- whatever M and DK"""
+    for nb in HEIGHTS:
+        if nb == 7:
+            continue
+        for dk in (2, 4, 6):
+            sides = {tg.kinv_in_lds(nb, dk, M, ig=True) for M in _height_range(nb)}
+            assert sides == {nb < 7}, (nb, dk, sides)
+
+
+def test_input_gradient_sub_tables_cover_what_they_are_for():
+    assert {(_nblk(n), tg.input_steps(tg.workload(tg.CASE_KW[n]).D)) for n in tg.IG_NO_BLDS_CASES} == \
+        {(nb, dk) for nb in (1, 2, 4) for dk in (2, 4, 6)}
+    assert sorted(_nblk(n) for n in tg.IG_STASH_CHUNK_CASES) == [13, 16, 20]
+    assert sorted(_nblk(n) for n in tg.IG_HALF_CASES) == HEIGHTS
+    assert {tg.input_steps(tg.workload(tg.CASE_KW[n]).D) for n in tg.IG_HALF_CASES} == {2, 4, 6}
+    assert all(_nblk(n) > 10 for n in tg.IG_PRSSM_CASES) and tg.IG_PRSSM_CASES
+    for n in tg.IG_STASH_CHUNK_CASES:       # enough steps and segments for several time-chunked launches
+        assert tg.CASE_KW[n]['T'] >= 6
 
 
 def test_sub_tables_cover_what_they_are_for():

@@ -17,6 +17,9 @@ loss_factors) is not zero, so the adjoint of the backward runs carries signal.  
 cond(K_mm + jitter I) < 1e6 for both GPs at the perturbed parameters (checked on the CPU): the 1e-6 gradient rule is
 stated for well-conditioned sets.
 
+The input-gradient adjoint (launch_revin_n) is a family of the same tree with its own LDS geometry: the IG_* tables below,
+proved complete by tests/test_tile_grid_cpu.py too, run by tests/test_input_grads_tile_grid_gpu.py.
+
 To extend: a new tile height, input width or trim makes test_tile_grid_cpu fail until CASES has a row that reaches it.
 """
 import os
@@ -100,6 +103,20 @@ GRAD_NOCOND_CASES = ['nb1_fill_dk4', 'nb2_first_dk4', 'nb4_mid_dk4', 'nb7_kt2_dk
 HALF_CASES = ['nb10_fill_dk4', 'nb13_first_dk4', 'nb16_first_dk6', 'nb20_mid_dk6', 'nb7_kt1_dk6', 'nb7_kt2_dk6',
               'nb7_kt1_dk2', 'nb7_kt2_dk2', 'nb7_kt1_dk4']
 
+# ---- the input-gradient family (launch_revin_n: rev_kernel<..., IG = true>; tests/test_input_grads_tile_grid_gpu.py) ---------
+# Every row of CASES runs with input_grads=True (GRAD_NOCOND_CASES also with `condition` False).  With IG the K^-1 image is
+# in LDS at every M of heights 1, 2, 4 and at no M of heights >= 10 (kinv_in_lds(..., ig=True)); at seven row blocks the
+# rows reach both placements by shape for every DK.  The streamed kernels of heights 1, 2, 4 run under CBFSSM_NO_BLDS=1,
+# every row of those heights once more (one per DK):
+IG_NO_BLDS_CASES = ['nb1_first_dk2', 'nb1_fill_dk4', 'nb1_mid_dk6', 'nb2_first_dk4', 'nb2_fill_dk6', 'nb2_mid_dk2',
+                    'nb4_first_dk6', 'nb4_fill_dk2', 'nb4_mid_dk4']
+# stash-mode time chunks (adjoint_stash_gib = 1e-9: one step / one segment per launch) at the heights above ten row blocks
+IG_STASH_CHUNK_CASES = ['nb13_mid_dk2', 'nb16_mid_dk4', 'nb20_mid_dk6']
+# forward-only variant (HipHalfGrad, 'rnn' recogniser; the MODE_FWD leaves with RevArgs::half): one row per tile height
+IG_HALF_CASES = ['nb1_mid_dk6', 'nb2_mid_dk2', 'nb4_mid_dk4', 'nb7_kt2_dk6', 'nb10_fill_dk4', 'nb13_fill_dk6',
+                 'nb16_fill_dk2', 'nb20_fill_dk4']
+IG_PRSSM_CASES = ['nb13_first_dk4']
+
 
 def workload(kw):
     return syn.tiny(**kw)
@@ -142,18 +159,25 @@ def leaf_keys(kw):
     return keys
 
 
+def revin_leaf_keys(kw, no_blds=False):
+    """The kernels (NBLK, DK, mode, K^-1 image in LDS) of launch_revin_k one row launches with input_grads=True."""
+    w = workload(kw)
+    return {(nb, dk, mode, (not no_blds) and kinv_in_lds(nb, dk, w.M, ig=True)) for nb, dk, _, _, mode in leaf_keys(kw)}
+
+
 def last_data_block(M):
     """row range [lo, M) of the last 16-row block that holds data: where padding and trimming act"""
     return 16 * ((M - 1) // 16), M
 
 
-def kinv_in_lds(nblk, dk, M):
+def kinv_in_lds(nblk, dk, M, ig=False):
     """launch_rev_k's `LDS_BASE + NBLK * KSr * 64 <= LDS_LIMIT` (csrc/cbfssm_adjoint_inst.hpp: RevGeom, RevCfg;
-    csrc/cbfssm_adjoint.hpp: RevInGeom) restated: True when the K^-1 image of the adjoint lives in LDS."""
+    csrc/cbfssm_adjoint.hpp: RevInGeom) restated: True when the K^-1 image of the adjoint lives in LDS.  ig: the same
+    switch of launch_revin_k, RevInGeom<DK, IG = true>: SPLITJ off, so PSL = max(JB, 2) * 256 and ECS = 0 at every width."""
     rb = 2 if nblk > 7 else 1
     waves = (nblk + rb - 1) // rb
     jb = (4 * dk + 1 + 15) // 16
-    splitj = jb == 2
+    splitj = jb == 2 and not ig
     psl = 272 if splitj else max(jb, 2) * 256
     ecs = 16 if splitj else 0
     base = 2 * 4 * dk * 17 + 2 * (16 * nblk) * 17 + 2 * 16 * 17 + waves * psl + 64 + waves * ecs
@@ -195,13 +219,18 @@ def _dispatch_heights(text, func):
 
 
 def compiled_families():
-    """{family: (tile heights, {(DK, mode)})} read from the source text of the four launcher families: float64 passes,
-    float64 adjoint, float32 passes, float32 adjoint.  Nothing is compiled or imported."""
+    """{family: (tile heights, {(DK, mode)})} read from the source text of the five launcher families: float64 passes,
+    float64 adjoint, float64 input-gradient adjoint (one revin_nb<N>.hip unit per height), float32 passes, float32
+    adjoint.  Nothing is compiled or imported."""
     inst, adj = _read('cbfssm_inst.hpp'), _read('cbfssm_adjoint_inst.hpp')
     families = {
         'pass': (_heights(inst, 'CBF_FOR_EACH_NBLK'), _switch_cases(inst, 'launch_pass_n')),
         'rev': (_heights(adj, 'CBF_FOR_EACH_REV_NBLK'), _switch_cases(adj, 'launch_rev_n')),
+        'revin': (_heights(adj, 'CBF_FOR_EACH_REV_NBLK'), _switch_cases(adj, 'launch_revin_n')),
     }
+    for nb in families['revin'][0]:
+        unit = 'revin_nb%d.hip' % nb
+        assert os.path.exists(os.path.join(CSRC, unit)) and 'CBF_REVIN_INSTANTIATE(%d)' % nb in _read(unit), unit
     for key, fname, func in (('pass32', 'cbfssm_f32.hip', 'launch32_n'), ('rev32', 'cbfssm_rev32.hip', 'launch_rev32_n')):
         text = _read(fname)
         families[key] = (_dispatch_heights(text, func), _switch_cases(text, func))
