@@ -1,6 +1,7 @@
 """Differentiable torch functions over the HIP library: the CBF-SSM loss of a whole engine (`elbo_loss`), the two
-functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down), its recurrence over time (`gp_rollout`) and the
-rigid-body filter loop of the Voliro model (`rigid_filter`, at the end).
+functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down), its recurrence over time (`gp_rollout`), the same
+recurrence with a masked Gaussian filter update per step (`gp_filter`) and the rigid-body filter loop of the Voliro model
+(`rigid_filter`, at the end).
 
 The CBF-SSM loss:
 
@@ -336,6 +337,151 @@ def gp_rollout_eval(pack, h0, a, eps, var_add, reverse=False):
         traj, _, ent = _rollout_forward(pack.layout, pack.buf, h0.contiguous(), a.contiguous() if a is not None else None,
                                         eps.contiguous(), var_add.contiguous() if var_add is not None else None, reverse, False)
     return traj, ent
+
+
+# ---- the filter loop of one sparse GP: the rollout with a Gaussian filter update per step and chain behind a mask --------
+#
+#     traj, kl = gp_filter(pack, h0, a, ytilde, eps, var_x, var_y, zeta_pos, zeta_mean, zeta_var_unc, variance_unc,
+#                          lengthscales_unc, cond=None, k_factor=1.0, reverse=False)
+#
+# the conditioned forward step of CBF-SSM (cbfssm/model/cbfssm.py:185-237) from per-chain data:
+#
+#     for t in 0..T-1 (reverse: T-1..0):
+#         fmean, fvar = predict(concat(h, a[t]));  m = h + fmean;  v = fvar + var_x
+#         cond[t, n]:  r = var_y + (k_factor - 1) v;  k = v / (r + v);  mu = m + k (ytilde[t] - m);  sig = (1 - k)^2 v + k^2 r
+#                      h = mu + eps[t] sqrt(sig);  kl += 0.5 (log v - log sig + (sig + (mu - m)^2) / v - 1)
+#         otherwise:   h = m + eps[t] sqrt(v)
+#         traj[t] = h
+#
+# h0 (N, Do), a (T, N, Da) (None or (T, N, 0) when Da = 0), ytilde (T, N, Do), eps (T, N) standard normals, var_x (Do)
+# CONSTRAINED values or None, var_y (Do) CONSTRAINED values, cond (T, N) of 0 / 1 (any dtype; None: condition everywhere).
+# A ytilde entry where cond = 0 is never used and may be NaN; its gradient is exactly 0.  Forward: cbfssm_gp_filter_f64,
+# the KL partials summed in a fixed order by cbfssm_reduce_partials_f64.  Backward: cbfssm_gp_filter_bwd_f64 ->
+# cbfssm_reduce_partials_f64 -> cbfssm_gp_tail_f64 (kl_weight 0); gradients for h0, a, ytilde, var_x, var_y and the five
+# parameter tensors, none for eps, cond, k_factor.  Once differentiable, no host synchronisation; the call keeps a copy of
+# the prepared pack, as gp_predict does.
+
+def _filter_forward(lay, buf, h0, a, ytilde, cond, eps, var_x, var_y, k_factor, reverse, save):
+    """(traj, msave or None, vsave or None, kl) of one forward launch on prepared pack operands"""
+    lib = _l.load()
+    T, N = eps.shape
+    Do, dev = lay.Do, eps.device
+    traj = torch.empty(T, N, Do, dtype=torch.float64, device=dev)
+    msave = torch.empty_like(traj) if save else None
+    vsave = torch.empty_like(traj) if save else None
+    if N == 0 or T == 0:
+        return traj, msave, vsave, torch.zeros((), dtype=torch.float64, device=dev)
+    npart = int(lib.cbfssm_gp_filter_partials(C.byref(lay), N))
+    if npart < 1:
+        raise _l.CbfssmHipError('cbfssm_gp_filter_partials refused the layout')
+    kl_part = torch.empty(npart + 32, dtype=torch.float64, device=dev)                      # (+ CBFSSM_REDUCE_SPLIT)
+    _l.check(lib.cbfssm_gp_filter_f64(C.byref(lay), _ptr(buf), _ptr(h0), _ptr(a), _ptr(ytilde), _ptr(cond), _ptr(eps),
+                                      _ptr(var_x), _ptr(var_y), float(k_factor), N, T, int(bool(reverse)), _ptr(traj),
+                                      _ptr(msave), _ptr(vsave), _ptr(kl_part), _stream()), 'cbfssm_gp_filter_f64')
+    kl = torch.empty(1, dtype=torch.float64, device=dev)
+    _l.check(lib.cbfssm_reduce_partials_f64(_ptr(kl_part), 1, npart, _ptr(kl), _stream()), 'cbfssm_reduce_partials_f64')
+    return traj, msave, vsave, kl.reshape(())
+
+
+def _filter_args(pack, h0, a, ytilde, eps, var_x, var_y, cond):
+    h0, a, eps, var_x = _rollout_args(pack, h0, a, eps, var_x)
+    dev = pack.buf.device
+    T, N = eps.shape
+    ytilde = torch.as_tensor(ytilde, dtype=torch.float64, device=dev)
+    var_y = torch.as_tensor(var_y, dtype=torch.float64, device=dev)
+    assert tuple(ytilde.shape) == (T, N, pack.Do) and tuple(var_y.shape) == (pack.Do,), 'ytilde (T, N, Do), var_y (Do)'
+    if cond is not None:
+        cond = torch.as_tensor(cond, device=dev)
+        assert tuple(cond.shape) == (T, N), 'cond (T, N)'
+        cond = (cond != 0).to(torch.float64).contiguous()
+    return h0, a, ytilde, eps, var_x, var_y, cond
+
+
+class _GpFilter(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, reverse, k_factor, cond, eps, h0, a, ytilde, var_x, var_y, *params):
+        pflat, cflat = _gp_flat(params)
+        h0d, epsd, ytd, vyd = (t.detach().contiguous() for t in (h0, eps, ytilde, var_y))
+        ad = a.detach().contiguous() if a is not None else None
+        vxd = var_x.detach().contiguous() if var_x is not None else None
+        buf = None
+        if eps.numel():                                 # (no chain or no step: nothing is prepared or launched)
+            _gp_prepare(pack, params, cflat)
+            buf = pack.buf.clone()
+        traj, msave, vsave, kl = _filter_forward(pack.layout, buf, h0d, ad, ytd, cond, epsd, vxd, vyd, k_factor, reverse, True)
+        ctx.layout, ctx.buf, ctx.reverse, ctx.k_factor = pack.layout, buf, bool(reverse), float(k_factor)
+        ctx.has_a, ctx.has_cond = ad is not None, cond is not None
+        ctx.save_for_backward(h0d, epsd, ytd, vyd, traj, msave, vsave, *([ad] if ad is not None else []),
+                              *([cond] if cond is not None else []))                         # (traj is an output)
+        ctx.pflat, ctx.cflat = pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in params)
+        return traj, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gtraj, gkl):
+        lib = _l.load()
+        lay, buf = ctx.layout, ctx.buf
+        h0, eps, ytilde, var_y, traj, msave, vsave = ctx.saved_tensors[:7]
+        rest = list(ctx.saved_tensors[7:])
+        a = rest.pop(0) if ctx.has_a else None
+        cond = rest.pop(0) if ctx.has_cond else None
+        need = ctx.needs_input_grad                     # 5 h0, 6 a, 7 ytilde, 8 var_x, 9 var_y, 10.. the leaves
+        T, N = eps.shape
+        dev = eps.device
+        gh0, gyt = torch.empty_like(h0), torch.empty_like(ytilde)
+        ga = torch.empty_like(a) if a is not None else None
+        gvx = gvy = None
+        gp = (None,) * 5
+        if N == 0 or T == 0:
+            gh0 = gtraj.new_zeros(h0.shape)
+            gvx, gvy = torch.zeros_like(var_y), torch.zeros_like(var_y)
+            gp = _gp_split(torch.zeros_like(ctx.pflat), ctx.shapes, need[10:])
+        else:
+            gtraj = gtraj.contiguous()
+            gkl = gkl.reshape(1).contiguous()
+            nwg = int(lib.cbfssm_gp_filter_bwd_workgroups(C.byref(lay), N))
+            nwork = int(lib.cbfssm_gp_filter_bwd_work_elems(C.byref(lay), N, T))
+            if nwg < 1 or nwork < 0:
+                raise _l.CbfssmHipError('cbfssm_gp_filter_bwd_workgroups / _work_elems refused the layout')
+            gpart = torch.empty((nwg + 32) * lay.rev_slab, dtype=torch.float64, device=dev)     # (+ CBFSSM_REDUCE_SPLIT)
+            work = torch.empty(nwork, dtype=torch.float64, device=dev) if nwork else None
+            image = torch.empty(lay.NBLK * lay.NBLK * 256, dtype=torch.float64, device=dev) if lay.rev_stash else None
+            _l.check(lib.cbfssm_gp_filter_bwd_f64(C.byref(lay), _ptr(buf), _ptr(h0), _ptr(a), _ptr(ytilde), _ptr(cond), _ptr(eps),
+                                                  _ptr(var_y), ctx.k_factor, _ptr(traj), _ptr(msave), _ptr(vsave), _ptr(gtraj),
+                                                  _ptr(gkl), N, T, int(ctx.reverse), _ptr(gh0), _ptr(ga), _ptr(gyt), _ptr(gpart),
+                                                  _ptr(work), _ptr(image), _stream()), 'cbfssm_gp_filter_bwd_f64')
+            if need[8] or need[9] or any(need[10:]):
+                red = torch.empty(lay.rev_slab, dtype=torch.float64, device=dev)
+                _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), lay.rev_slab, nwg, _ptr(red), _stream()),
+                         'cbfssm_reduce_partials_f64')
+                small = lay.rev_slab - 192              # the slab's scalars: [0, 16) d/d var_x, [16, 32) d/d var_y by state dim
+                gvx = red[small:small + lay.Do].clone()
+                gvy = red[small + 16:small + 16 + lay.Do].clone()
+                if any(need[10:]):
+                    gp = _gp_split(_gp_tail(lay, buf, red, image, 0.0, ctx.pflat, ctx.cflat), ctx.shapes, need[10:])
+        return (None, None, None, None, None, gh0 if need[5] else None, ga if need[6] else None, gyt if need[7] else None,
+                gvx if need[8] else None, gvy if need[9] else None) + gp
+
+
+def gp_filter(pack, h0, a, ytilde, eps, var_x, var_y, *params, cond=None, k_factor=1.0, reverse=False):
+    """(traj (T, N, Do), kl ()) of the loop above with a grad_fn into h0, a, ytilde, var_x, var_y and the five parameter
+    tensors."""
+    h0, a, ytilde, eps, var_x, var_y, cond = _filter_args(pack, h0, a, ytilde, eps, var_x, var_y, cond)
+    return _GpFilter.apply(pack, bool(reverse), float(k_factor), cond, eps.detach(), h0, a, ytilde, var_x, var_y,
+                           *_gp_args(pack, params))
+
+
+def gp_filter_eval(pack, h0, a, ytilde, eps, var_x, var_y, cond=None, k_factor=1.0, reverse=False):
+    """The forward launch alone on a pack that is already prepared: no saved rows, no grad_fn."""
+    h0, a, ytilde, eps, var_x, var_y, cond = _filter_args(pack, h0, a, ytilde, eps, var_x, var_y, cond)
+    with torch.no_grad():
+        traj, _, _, kl = _filter_forward(pack.layout, pack.buf, h0.contiguous(), a.contiguous() if a is not None else None,
+                                         ytilde.contiguous(), cond, eps.contiguous(),
+                                         var_x.contiguous() if var_x is not None else None, var_y.contiguous(), k_factor,
+                                         reverse, False)
+    return traj, kl
 
 
 # ---- Voliro's forward filter run: rigid-body step, Gaussian filter update, one sample and a KL term per step -------------

@@ -32,6 +32,8 @@ SYMBOLS = (
     'cbfssm_gp_predict_bwd_workgroups', 'cbfssm_gp_predict_bwd_work_elems', 'cbfssm_gp_predict_bwd_f64', 'cbfssm_gp_tail_f64',
     'cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_f64', 'cbfssm_gp_rollout_bwd_workgroups', 'cbfssm_gp_rollout_bwd_work_elems',
     'cbfssm_gp_rollout_bwd_f64',
+    'cbfssm_gp_filter_partials', 'cbfssm_gp_filter_f64', 'cbfssm_gp_filter_bwd_workgroups', 'cbfssm_gp_filter_bwd_work_elems',
+    'cbfssm_gp_filter_bwd_f64',
     'cbfssm_rigid_filter_partials', 'cbfssm_rigid_filter_f64', 'cbfssm_rigid_filter_bwd_f64',
     'cbfssm_gru_recog_bwd_in_f64', 'cbfssm_conv_recog_bwd_in_f32', 'cbfssm_half_forward_pass_bwd_in_f64',
     'cbfssm_half_input_grads_f64',
@@ -178,6 +180,13 @@ def load():
     lib.cbfssm_gp_rollout_bwd_work_elems.argtypes = [C.POINTER(PackLayout), i64, i64]
     lib.cbfssm_gp_rollout_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, vp, vp, i64, i64, ip, vp, vp, vp, vp]
     lib.cbfssm_gp_rollout_bwd_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [i64, i64, ip] + [vp] * 6
+    for name in ('cbfssm_gp_filter_partials', 'cbfssm_gp_filter_bwd_workgroups'):
+        getattr(lib, name).restype = i64
+        getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]
+    lib.cbfssm_gp_filter_bwd_work_elems.restype = i64
+    lib.cbfssm_gp_filter_bwd_work_elems.argtypes = [C.POINTER(PackLayout), i64, i64]
+    lib.cbfssm_gp_filter_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [dbl, i64, i64, ip] + [vp] * 5
+    lib.cbfssm_gp_filter_bwd_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 7 + [dbl] + [vp] * 5 + [i64, i64, ip] + [vp] * 7
     lib.cbfssm_rigid_filter_partials.restype = i64
     lib.cbfssm_rigid_filter_partials.argtypes = [i64]
     lib.cbfssm_rigid_filter_f64.argtypes = [C.POINTER(RigidBody)] + [vp] * 6 + [i64, i64] + [vp] * 3

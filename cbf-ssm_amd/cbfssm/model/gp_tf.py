@@ -208,3 +208,28 @@ class GPModel:
         if self._wants_grad(h0, a, var_add):
             return _ag.gp_rollout(self._pack, h0, a, eps, var_add, *self.parameters(), reverse=reverse)
         return _ag.gp_rollout_eval(self._prepared(), h0, a, eps, var_add, reverse=reverse)
+
+    def filter(self, h0, a, ytilde, eps, var_x, var_y, cond=None, k_factor=1.0, reverse=False):
+        """An addition to the reference's surface: the conditioned forward step of CBF-SSM (cbfssm/model/cbfssm.py:185-237)
+        over this GP from per-chain data, as one launch:
+
+            for t in 0..T-1 (reverse: T-1..0):
+                fmean, fvar = predict(concat(h, a[t]));  m = h + fmean;  v = fvar + var_x
+                where cond[t, n]:  r = var_y + (k_factor - 1) v;  k = v / (r + v);  mu = m + k (ytilde[t] - m)
+                                   sig = (1 - k)^2 v + k^2 r;  h = mu + eps[t][:, None] * sqrt(sig)
+                                   kl += 0.5 (log v - log sig + (sig + (mu - m)^2) / v - 1)
+                elsewhere:         h = m + eps[t][:, None] * sqrt(v)
+                traj[t] = h
+
+        h0 (N, out_dim), a (T, N, in_dim - out_dim) or None, ytilde (T, N, out_dim), eps (T, N) standard normals, var_x
+        (out_dim) constrained values or None, var_y (out_dim) constrained values, cond (T, N) of 0 / 1 or None (condition
+        everywhere): a prefix of ones is warm-up then forecast, zeros mark missing observations -- ytilde may hold NaN
+        there, it is never read into a result.  Returns (traj (T, N, out_dim), kl ()).  When a leaf, h0, a, ytilde, var_x or
+        var_y requires grad both results carry a grad_fn (cbfssm.hip.autograd.gp_filter; eps, cond and k_factor get no
+        gradient); otherwise the forward kernel runs alone and keeps nothing for an adjoint."""
+        from ..hip import autograd as _ag
+        if self._wants_grad(h0, a, ytilde, var_x, var_y):
+            return _ag.gp_filter(self._pack, h0, a, ytilde, eps, var_x, var_y, *self.parameters(), cond=cond,
+                                 k_factor=k_factor, reverse=reverse)
+        pack = self._prepared() if torch.as_tensor(eps).numel() else self._pack      # (nothing runs without a chain or a step)
+        return _ag.gp_filter_eval(pack, h0, a, ytilde, eps, var_x, var_y, cond=cond, k_factor=k_factor, reverse=reverse)

@@ -1,0 +1,157 @@
+// Host side of the fused GP filter loop and its adjoint (cbfssm_gp_filter.hpp): argument checks, grids, stash contraction.
+#include <hip/hip_runtime.h>
+#include <cstring>
+#include "../../include/cbfssm_hip.h"
+#include "cbfssm_gp_filter.hpp"
+
+CBF_FOR_EACH_GPBWD_NBLK(CBF_GPFILT_DECLARE)
+
+namespace cbfssm {
+
+int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
+
+static const int64_t kMaxChains = int64_t(1) << 30;    // as the pass kernels
+static const int64_t kMaxSteps = int64_t(1) << 24;
+
+static int dispatch_gp_filt(int NBLK, int DK, const GpFiltArgs& a, hipStream_t st)
+{
+    switch (NBLK) {
+#define X(NB) case NB: return launch_gp_filt_nb##NB(DK, a, st);
+        CBF_FOR_EACH_GPBWD_NBLK(X)
+#undef X
+    }
+    return -3;
+}
+
+static int dispatch_gp_filt_bwd(int NBLK, int DK, const GpFiltBwdArgs& a, hipStream_t st)
+{
+    switch (NBLK) {
+#define X(NB) case NB: return launch_gp_filt_bwd_nb##NB(DK, a, st);
+        CBF_FOR_EACH_GPBWD_NBLK(X)
+#undef X
+    }
+    return -3;
+}
+
+// the limits of cbfssm_gp_predict_f64, checked on the layout itself (a layout need not come from cbfssm_gp_pack_layout)
+static bool gp_filt_layout_ok(const cbfssm_pack_layout* L)
+{
+    if (!L) return false;
+    if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
+    if (L->Do > L->D) return false;
+    bool nb = false;
+#define X(NB) nb = nb || (L->NBLK == NB);
+    CBF_FOR_EACH_GPBWD_NBLK(X)
+#undef X
+    if (!nb || 16 * L->NBLK < L->M || L->KS != 4 * L->NBLK) return false;
+    if ((L->DK != 2 && L->DK != 4 && L->DK != 6) || 4 * L->DK < L->D) return false;
+    if (L->JB != (4 * L->DK + 1 + 15) / 16 || L->rev_slab <= 0 || (L->rev_stash != 0) != (L->NBLK > 7)) return false;
+    if (L->gp_form != CBFSSM_GP_FORM_DENSE && L->gp_form != CBFSSM_GP_FORM_TRI) return false;
+    return true;
+}
+
+static int check_sizes(const cbfssm_pack_layout* L, int64_t N, int64_t T, const char* who)
+{
+    if (!L) return fail(-1, "%s: null layout", who);
+    if (!gp_filt_layout_ok(L))
+        return fail(-3, "%s limits: M <= %d, Do <= D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
+                    who, CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
+    if (N < 0 || T < 1) return fail(-1, "%s: N=%lld must be >= 0 and T=%lld >= 1", who, (long long)N, (long long)T);
+    if (N > kMaxChains || T > kMaxSteps) return fail(-3, "%s: N <= 2^30 chains, T <= 2^24 steps", who);
+    return 0;
+}
+
+static void set_pack(PackPtrs& pk, const cbfssm_pack_layout* L, const double* pack)
+{
+    pk.Bp = pack + L->Bp; pk.Zp = pack + L->Zp; pk.cz = pack + L->cz; pk.muA = pack + L->muA; pk.s2A = pack + L->s2A;
+    pk.invl = pack + L->invl; pk.scal = pack + L->scal; pk.KSr = (L->M + 3) / 4;
+    pk.Wp = pack + L->Wp; pk.WTp = pack + L->WTp;
+}
+
+}  // namespace cbfssm
+
+using namespace cbfssm;
+
+extern "C" {
+
+int64_t cbfssm_gp_filter_partials(const cbfssm_pack_layout* L, int64_t N)
+{
+    if (!gp_filt_layout_ok(L) || N < 0 || N > kMaxChains) return -1;
+    return (N + 15) / 16;
+}
+
+int64_t cbfssm_gp_filter_bwd_workgroups(const cbfssm_pack_layout* L, int64_t N)
+{
+    if (!gp_filt_layout_ok(L) || N < 0 || N > kMaxChains) return -1;
+    return (N + 15) / 16;
+}
+
+int64_t cbfssm_gp_filter_bwd_work_elems(const cbfssm_pack_layout* L, int64_t N, int64_t T)
+{
+    if (!gp_filt_layout_ok(L) || N < 0 || N > kMaxChains || T < 0 || T > kMaxSteps) return -1;
+    if (!L->rev_stash) return 0;
+    const int64_t nslots = (N + 15) / 16 * T;
+    return 2 * nslots * L->NBLK * 256 + cbfssm_stash_contract_work_elems(L, nslots);
+}
+
+int cbfssm_gp_filter_f64(const cbfssm_pack_layout* L, const double* pack, const double* h0, const double* a,
+                         const double* ytilde, const double* cond, const double* eps, const double* var_x,
+                         const double* var_y, double k_factor, int64_t N, int64_t T, int reverse, double* traj,
+                         double* msave, double* vsave, double* kl_part, void* stream)
+{
+    int rc = check_sizes(L, N, T, "gp_filter");
+    if (rc) return rc;
+    if (!pack || !h0 || !ytilde || !eps || !var_y || !traj || !kl_part) return fail(-1, "gp_filter: null pointer");
+    if ((msave == nullptr) != (vsave == nullptr)) return fail(-1, "gp_filter: msave and vsave are given or left out together");
+    if (L->D > L->Do && !a) return fail(-1, "gp_filter: D=%d > Do=%d needs the auxiliary inputs a", L->D, L->Do);
+    if (N == 0) return 0;
+    GpFiltArgs g;
+    memset(&g, 0, sizeof(g));
+    set_pack(g.pk, L, pack);
+    g.h0 = h0; g.a = a; g.ytilde = ytilde; g.cond = cond; g.eps = eps; g.var_x = var_x; g.var_y = var_y;
+    g.k_factor = k_factor;
+    g.traj = traj; g.msave = msave; g.vsave = vsave; g.kl_part = kl_part;
+    g.N = int(N); g.T = int(T); g.D = L->D; g.Do = L->Do; g.reverse = reverse ? 1 : 0;
+    g.tri = (L->gp_form == CBFSSM_GP_FORM_TRI);
+    rc = dispatch_gp_filt(L->NBLK, L->DK, g, (hipStream_t)stream);
+    if (rc) return fail(rc, "gp_filter launch failed (NBLK=%d DK=%d rc=%d)", L->NBLK, L->DK, rc);
+    return 0;
+}
+
+int cbfssm_gp_filter_bwd_f64(const cbfssm_pack_layout* L, const double* pack, const double* h0, const double* a,
+                             const double* ytilde, const double* cond, const double* eps, const double* var_y,
+                             double k_factor, const double* traj, const double* msave, const double* vsave,
+                             const double* gtraj, const double* g_kl, int64_t N, int64_t T, int reverse, double* gh0,
+                             double* ga, double* gytilde, double* gpart, double* work, double* gB_image, void* stream)
+{
+    int rc = check_sizes(L, N, T, "gp_filter_bwd");
+    if (rc) return rc;
+    if (!pack || !h0 || !ytilde || !eps || !var_y || !traj || !msave || !vsave || !gtraj || !g_kl || !gh0 || !gytilde || !gpart)
+        return fail(-1, "gp_filter_bwd: null pointer");
+    if (L->D > L->Do && (!a || !ga)) return fail(-1, "gp_filter_bwd: D=%d > Do=%d needs a and ga", L->D, L->Do);
+    if (L->rev_stash && (!work || !gB_image)) return fail(-1, "gp_filter_bwd: M=%d (> 112) needs work and gB_image", L->M);
+    if (N == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    GpFiltBwdArgs g;
+    memset(&g, 0, sizeof(g));
+    set_pack(g.pk, L, pack);
+    g.rk.muB = pack + L->muB; g.rk.s2B = pack + L->s2B; g.rk.ZT = pack + L->ZT;
+    g.h0 = h0; g.a = a; g.ytilde = ytilde; g.cond = cond; g.eps = eps; g.var_y = var_y; g.k_factor = k_factor;
+    g.traj = traj; g.msave = msave; g.vsave = vsave; g.gtraj = gtraj; g.g_kl = g_kl;
+    g.gh0 = gh0; g.ga = ga; g.gytilde = gytilde; g.gpart = gpart; g.slab = L->rev_slab;
+    g.N = int(N); g.T = int(T); g.M = L->M; g.D = L->D; g.Do = L->Do; g.reverse = reverse ? 1 : 0;
+    const int64_t nslots = (N + 15) / 16 * T;
+    if (L->rev_stash) {
+        g.stash_a = work;
+        g.stash_k = work + nslots * L->NBLK * 256;
+        hipError_t e = hipMemsetAsync(gB_image, 0, size_t(L->NBLK) * L->NBLK * 256 * sizeof(double), st);
+        if (e != hipSuccess) return fail(-int(e) - 1000, "gp_filter_bwd: clearing the K^-1 adjoint image failed");
+    }
+    rc = dispatch_gp_filt_bwd(L->NBLK, L->DK, g, st);
+    if (rc) return fail(rc, "gp_filter_bwd launch failed (NBLK=%d DK=%d rc=%d)", L->NBLK, L->DK, rc);
+    if (L->rev_stash)
+        return cbfssm_stash_contract_f64(L, g.stash_a, g.stash_k, nslots, work + 2 * nslots * L->NBLK * 256, gB_image, stream);
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,2 @@
+#include "cbfssm_gp_filter.hpp"
+CBF_GPFILT_INSTANTIATE(1)

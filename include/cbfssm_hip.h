@@ -225,6 +225,58 @@ int cbfssm_gp_rollout_bwd_f64(const cbfssm_pack_layout* layout, const double* pa
                               double* gpart, double* work, double* gB_image, void* stream);
 
 /*
+ * ---- differentiable GP filter loop: the rollout above with a Gaussian filter update per step and chain behind a mask.
+ * The conditioned forward step of CBF-SSM (cbfssm/model/cbfssm.py:185-237) for per-chain inputs, differentiable
+ * pseudo-observations and a per-(step, chain) mask: state estimation with a GP transition, warm-up then forecast
+ * (cond = 1 on the first K steps), missing observations (cond = 0 where there is no data).
+ *
+ *   for t = 0 .. T-1 (reverse != 0: T-1 .. 0):
+ *       fmean, fvar = GPModel.predict(concat(h, a[t]));  m = h + fmean;  v = fvar + var_x        cbfssm.py:199-206
+ *       cond[t, n] != 0:  r = var_y + (k_factor - 1) v;  s = r + v;  k = v / s;  delta = ytilde[t] - m     :212-217
+ *                         mu = m + k delta;  sig = (1 - k)^2 v + k^2 r;  h = mu + eps[t] sqrt(sig)         :218-221
+ *                         kl += 0.5 (log v - log sig + (sig + (mu - m)^2) / v - 1)                         :232-234
+ *       otherwise:        h = m + eps[t] sqrt(v)                                                           :224
+ *       traj[t] = h
+ *
+ * cbfssm_gp_filter_f64 (cbfssm.py:185-237): h0 (N, Do), a (T, N, Da) with Da = D - Do (NULL when Da = 0), ytilde
+ * (T, N, Do), cond (T, N) doubles 0 / 1 or NULL = condition everywhere, eps (T, N), var_x (Do) constrained values or
+ * NULL, var_y (Do) constrained values, k_factor by value -> traj (T, N, Do), every entry written once; msave, vsave
+ * (T, N, Do), or both NULL: m and v of every step, kept for the adjoint; kl_part: cbfssm_gp_filter_partials doubles, one
+ * partial per 16 chains, whose sum is `kl` (cbfssm_reduce_partials_f64 with slab 1; NaN when a hand-off poll of the
+ * two-triangular form ran out).  The branch is a select: a ytilde entry at cond = 0 may be NaN and reaches no output.
+ * One launch, one workgroup per 16 chains, both GP forms (layout->gp_form).  cond = 0 everywhere is
+ * cbfssm_gp_rollout_f64 without the entropy.
+ *
+ * cbfssm_gp_filter_bwd_f64 (cbfssm.py:185-237 differentiated): pack, h0, a, ytilde, cond, eps, var_y, k_factor, traj,
+ * msave, vsave as in / from the forward call, gtraj (T, N, Do) = d loss / d traj, g_kl: ONE double on the device =
+ * d loss / d kl
+ *   -> gh0 (N, Do), ga (T, N, Da; NULL when Da = 0), gytilde (T, N, Do; exactly 0 where cond = 0): every entry written once;
+ *      gpart: cbfssm_gp_filter_bwd_workgroups slabs of layout->rev_slab doubles ("Slab layout of the parameter adjoints of
+ *      one GP" below) with room for CBFSSM_REDUCE_SPLIT more; the d/d var_x and d/d var_y entries hold d loss / d var_x
+ *      and d loss / d var_y by state dim; cbfssm_reduce_partials_f64 and cbfssm_gp_tail_f64 (kl_weight 0) take them as
+ *      they are;
+ *      M > 112 (layout->rev_stash): work (cbfssm_gp_filter_bwd_work_elems doubles) and gB_image ([NBLK][NBLK][4][64],
+ *      cleared by the call) as in cbfssm_gp_rollout_bwd_f64; otherwise both may be NULL.
+ * delta, k and sig are recomputed from msave / vsave, the kernel tile and A2 = K^-1 k of every step from the trajectory.
+ * No atomics, no host synchronisation; two calls are bitwise identical.  eps, cond and k_factor have no adjoint.
+ * Counts and error codes as the rollout's: -1 for a bad layout or a negative size from the three counts; the calls: NULL
+ * pointers and T < 1 -> -1; beyond M <= 320, Do <= D <= 24, Do <= 16 or N > 2^30, T > 2^24 -> -3, before any launch.
+ */
+int64_t cbfssm_gp_filter_partials(const cbfssm_pack_layout* layout, int64_t N);                   /* cbfssm.py:185-237 */
+int cbfssm_gp_filter_f64(const cbfssm_pack_layout* layout, const double* pack, const double* h0, const double* a,
+                         const double* ytilde, const double* cond, const double* eps, const double* var_x,
+                         const double* var_y, double k_factor, int64_t N, int64_t T, int reverse, double* traj,
+                         double* msave, double* vsave, double* kl_part, void* stream);           /* cbfssm.py:185-237 */
+int64_t cbfssm_gp_filter_bwd_workgroups(const cbfssm_pack_layout* layout, int64_t N);             /* cbfssm.py:185-237 */
+int64_t cbfssm_gp_filter_bwd_work_elems(const cbfssm_pack_layout* layout, int64_t N, int64_t T);  /* cbfssm.py:185-237 */
+int cbfssm_gp_filter_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* h0, const double* a,
+                             const double* ytilde, const double* cond, const double* eps, const double* var_y,
+                             double k_factor, const double* traj, const double* msave, const double* vsave,
+                             const double* gtraj, const double* g_kl, int64_t N, int64_t T, int reverse, double* gh0,
+                             double* ga, double* gytilde, double* gpart, double* work, double* gB_image,
+                             void* stream);                                                      /* cbfssm.py:185-237 */
+
+/*
  * ---- Voliro's forward filter run: the rigid-body time loop and its adjoint.
  * Replaces _forward / _forward_body / symplectic_euler of the reference's fourth model (cbfssm/model/voliro.py:188-242,
  * 314-338 with cbfssm/utils/quaternions.py), for S = T - 1 steps and N = B * samples chains:
