@@ -1,5 +1,6 @@
 """Differentiable torch functions over the HIP library: the CBF-SSM loss of a whole engine (`elbo_loss`), the two
-functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down), its recurrence over time (`gp_rollout`), the same
+functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down; `gp_predict_fullq`, `gp_prior_kl_fullq` with a
+full-covariance q(z), `gp_conditional_diag` behind `gp_tf.conditional`), its recurrence over time (`gp_rollout`), the same
 recurrence with a masked Gaussian filter update per step (`gp_filter`) and the rigid-body filter loop of the Voliro model
 (`rigid_filter`, at the end).
 
@@ -205,6 +206,283 @@ def gp_predict(pack, X, *params):
 def gp_prior_kl(pack, *params):
     """GPModel.prior_kl() as a 0-d tensor with a grad_fn into the five parameter tensors."""
     return _GpPriorKl.apply(pack, *_gp_args(pack, params))
+
+
+# ---- one sparse GP with a full-covariance q(z): conditional() with q_sqrt (Do, M, M) (gp_tf.py:68-100) and the
+# zeta_std.ndims == 3 branch of GPModel.predict (gp_tf.py:150-159) as torch functions ---------------------------------------
+#
+#     fmean, fvar = gp_predict_fullq(pack, X, zeta_pos, zeta_mean, q_sqrt, variance_unc, lengthscales_unc)
+#     kl = gp_prior_kl_fullq(pack, zeta_pos, zeta_mean, q_sqrt, variance_unc, lengthscales_unc)
+#
+# q_sqrt holds the lower-triangular factors L_d, unconstrained; entries above the diagonal are never read and their gradient
+# is exactly zero.  Forward of gp_predict_fullq: cbfssm_gp_fullq_prepare_f64 (S_d images, kept for the backward), then
+# cbfssm_gp_fullq_predict_f64 on the f64 MFMA units.  Backward: cbfssm_gp_fullq_bwd_f64 -> cbfssm_reduce_partials_f64 ->
+# cbfssm_gp_tail_fullq_f64 (kl_weight 0) for the four GP tensors, cbfssm_gp_fullq_wd_f64 -> cbfssm_gp_fullq_lbar_f64 for
+# q_sqrt.  gp_prior_kl_fullq: cbfssm_gp_fullq_kl_f64; backward cbfssm_gp_tail_fullq_f64 without a slab (kl_weight 1) and
+# cbfssm_gp_fullq_lbar_f64 without W.  As above: no host synchronisation, a copy of the prepared pack per call, once
+# differentiable, only the requested gradients.
+
+GP_FULLQ_PARAM_NAMES = ('zeta_pos', 'zeta_mean', 'zeta_sqrt', 'variance_unc', 'lengthscales_unc')
+
+
+def _fq_flat(pack, zp, zm, var, ls):
+    """(pflat, cflat) in cbfssm_gp_tail_fullq_f64's order: the zeta_var segment is a placeholder that no kernel reads"""
+    hole = torch.zeros(pack.M * pack.Do, dtype=torch.float64, device=pack.buf.device)
+    zp, zm, var, ls = [p.detach().reshape(-1) for p in (zp, zm, var, ls)]
+    pflat = torch.cat([zp, zm, hole, var, ls]).contiguous()
+    cflat = torch.cat([zp, zm, hole, tf_forward(var), tf_forward(ls)]).contiguous()
+    return pflat, cflat
+
+
+def _fq_prepare(pack, zp, zm, q, var, ls):
+    M, D, Do = pack.M, pack.D, pack.Do
+    assert tuple(zp.shape) == (M, D) and tuple(zm.shape) == (M, Do) and tuple(q.shape) == (Do, M, M)
+    assert var.numel() == 1 and ls.numel() == D
+    pflat, cflat = _fq_flat(pack, zp, zm, var, ls)
+    o1, o2, o3 = M * D, M * D + M * Do, M * D + 2 * M * Do
+    pack.prepare(cflat[:o1].view(M, D), cflat[o3 + 1:], cflat[o3:o3 + 1], cflat[o1:o2].view(M, Do), cflat[o2:o3].view(M, Do))
+    return pflat, cflat
+
+
+def _fq_qpack(lay, q):
+    lib = _l.load()
+    n = int(lib.cbfssm_gp_fullq_pack_elems(C.byref(lay)))
+    if n < 1:
+        raise _l.CbfssmHipError('cbfssm_gp_fullq_pack_elems refused the layout')
+    qpack = torch.empty(n, dtype=torch.float64, device=q.device)
+    _l.check(lib.cbfssm_gp_fullq_prepare_f64(C.byref(lay), _ptr(q), _ptr(qpack), _stream()), 'cbfssm_gp_fullq_prepare_f64')
+    return qpack
+
+
+def _fq_forward(lay, buf, qpack, X):
+    """(fmean, fvar) of cbfssm_gp_fullq_predict_f64 on a prepared pack and q pack; nothing is launched without a point"""
+    n = X.shape[0]
+    fmean = torch.empty(n, lay.Do, dtype=torch.float64, device=buf.device)
+    fvar = torch.empty_like(fmean)
+    if n:
+        _l.check(_l.load().cbfssm_gp_fullq_predict_f64(C.byref(lay), _ptr(buf), _ptr(qpack), _ptr(X), n, _ptr(fmean), _ptr(fvar),
+                                                       _stream()), 'cbfssm_gp_fullq_predict_f64')
+    return fmean, fvar
+
+
+def _fq_kl(lay, buf, q, qpack, zeta_mean):
+    kl = torch.empty(1, dtype=torch.float64, device=buf.device)
+    _l.check(_l.load().cbfssm_gp_fullq_kl_f64(C.byref(lay), _ptr(buf), _ptr(q), _ptr(qpack), _ptr(zeta_mean), _ptr(kl), _stream()),
+             'cbfssm_gp_fullq_kl_f64')
+    return kl.reshape(())
+
+
+def gp_fullq_eval(pack, X, q_sqrt, zeta_mean):
+    """Evaluation only, on a PREPARED pack: (fmean, fvar) at X when X is given, else the prior KL.  Keeps nothing."""
+    q = q_sqrt.detach().contiguous()
+    if X is not None and X.shape[0] == 0:
+        return _fq_forward(pack.layout, pack.buf, None, X)
+    qpack = _fq_qpack(pack.layout, q)
+    if X is not None:
+        return _fq_forward(pack.layout, pack.buf, qpack, X.detach().contiguous())
+    return _fq_kl(pack.layout, pack.buf, q, qpack, zeta_mean.detach().contiguous())
+
+
+def _fq_tail(lay, buf, qpack, red, image, kl_weight, pflat, cflat):
+    lib = _l.load()
+    work = torch.empty(int(lib.cbfssm_train_tail_half_work_elems(C.byref(lay))), dtype=torch.float64, device=buf.device)
+    gflat = torch.empty_like(pflat)
+    _l.check(lib.cbfssm_gp_tail_fullq_f64(C.byref(lay), _ptr(buf), _ptr(qpack), _ptr(red), _ptr(image), 0, float(kl_weight),
+                                          _ptr(pflat), _ptr(cflat), _ptr(work), _ptr(gflat), _stream()),
+             'cbfssm_gp_tail_fullq_f64')
+    return gflat
+
+
+def _fq_split(gflat, gq, shapes, need):
+    """gradients in the order (zeta_pos, zeta_mean, q_sqrt, variance_unc, lengthscales_unc)"""
+    M_Do = shapes[1]
+    gp = (None,) * 5 if gflat is None else _gp_split(gflat, (shapes[0], shapes[1], M_Do, shapes[3], shapes[4]),
+                                                     (need[0], need[1], False, need[3], need[4]))
+    return (gp[0], gp[1], gq if need[2] else None, gp[3], gp[4])
+
+
+class _GpPredictFullq(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, X, zp, zm, q, var, ls):
+        lib = _l.load()
+        pflat, cflat = _fq_prepare(pack, zp, zm, q, var, ls)
+        Xd, qd = X.detach().contiguous(), q.detach().contiguous().clone()
+        lay, n = pack.layout, X.shape[0]
+        qpack = _fq_qpack(lay, qd) if n else None                            # (no launch without a point)
+        fmean, fvar = _fq_forward(lay, pack.buf, qpack, Xd)
+        ctx.layout, ctx.buf, ctx.qpack = lay, pack.buf.clone(), qpack
+        ctx.X, ctx.q, ctx.pflat, ctx.cflat = Xd, qd, pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in (zp, zm, q, var, ls))
+        return fmean, fvar
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gmean, gvar):
+        lib = _l.load()
+        lay, buf, X, q = ctx.layout, ctx.buf, ctx.X, ctx.q
+        need = ctx.needs_input_grad
+        n, dev = X.shape[0], X.device
+        gX = torch.empty_like(X)
+        if n == 0:
+            gp = _fq_split(torch.zeros_like(ctx.pflat), torch.zeros_like(q), ctx.shapes, need[2:])
+            return (None, gX if need[1] else None) + gp
+        gmean, gvar = gmean.contiguous(), gvar.contiguous()
+        nwg = int(lib.cbfssm_gp_fullq_bwd_workgroups(C.byref(lay), n))
+        nwork = int(lib.cbfssm_gp_fullq_bwd_work_elems(C.byref(lay), n))
+        na2 = int(lib.cbfssm_gp_fullq_a2_elems(C.byref(lay), n))
+        if nwg < 1 or nwork < 0 or na2 < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_fullq_bwd_workgroups / _work_elems / _a2_elems refused the layout')
+        qpack = ctx.qpack
+        gpart = torch.empty((nwg + 32) * lay.rev_slab, dtype=torch.float64, device=dev)     # (+ CBFSSM_REDUCE_SPLIT)
+        a2 = torch.empty(na2, dtype=torch.float64, device=dev)
+        work = torch.empty(nwork, dtype=torch.float64, device=dev) if nwork else None
+        image = torch.empty(lay.NBLK * lay.NBLK * 256, dtype=torch.float64, device=dev) if lay.rev_stash else None
+        _l.check(lib.cbfssm_gp_fullq_bwd_f64(C.byref(lay), _ptr(buf), _ptr(qpack), _ptr(X), n, _ptr(gmean), _ptr(gvar),
+                                             _ptr(gX), _ptr(gpart), _ptr(a2), _ptr(work), _ptr(image), _stream()),
+                 'cbfssm_gp_fullq_bwd_f64')
+        gflat = gq = None
+        if need[2] or need[3] or need[5] or need[6]:
+            red = torch.empty(lay.rev_slab, dtype=torch.float64, device=dev)
+            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), lay.rev_slab, nwg, _ptr(red), _stream()),
+                     'cbfssm_reduce_partials_f64')
+            gflat = _fq_tail(lay, buf, qpack, red, image, 0.0, ctx.pflat, ctx.cflat)
+        if need[4]:
+            wwork = torch.empty(int(lib.cbfssm_gp_fullq_wd_work_elems(C.byref(lay), n)), dtype=torch.float64, device=dev)
+            W = torch.empty_like(q)
+            _l.check(lib.cbfssm_gp_fullq_wd_f64(C.byref(lay), _ptr(a2), _ptr(gvar), n, _ptr(wwork), _ptr(W), _stream()),
+                     'cbfssm_gp_fullq_wd_f64')
+            gq = torch.empty_like(q)
+            _l.check(lib.cbfssm_gp_fullq_lbar_f64(C.byref(lay), None, _ptr(q), _ptr(W), 0.0, _ptr(gq), _stream()),
+                     'cbfssm_gp_fullq_lbar_f64')
+        return (None, gX if need[1] else None) + _fq_split(gflat, gq, ctx.shapes, need[2:])
+
+
+class _GpPriorKlFullq(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, zp, zm, q, var, ls):
+        lib = _l.load()
+        pflat, cflat = _fq_prepare(pack, zp, zm, q, var, ls)
+        qd = q.detach().contiguous().clone()
+        lay = pack.layout
+        qpack = _fq_qpack(lay, qd)
+        o1 = pack.M * pack.D
+        kl = _fq_kl(lay, pack.buf, qd, qpack, cflat[o1:o1 + pack.M * pack.Do])
+        ctx.layout, ctx.buf = lay, pack.buf.clone()
+        ctx.q, ctx.qpack, ctx.pflat, ctx.cflat = qd, qpack, pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in (zp, zm, q, var, ls))
+        return kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        lib = _l.load()
+        need = ctx.needs_input_grad[1:]
+        gflat = gq = None
+        if need[0] or need[1] or need[3] or need[4]:
+            gflat = _fq_tail(ctx.layout, ctx.buf, ctx.qpack, None, None, 1.0, ctx.pflat, ctx.cflat) * gout
+        if need[2]:
+            gq = torch.empty_like(ctx.q)
+            _l.check(lib.cbfssm_gp_fullq_lbar_f64(C.byref(ctx.layout), _ptr(ctx.buf), _ptr(ctx.q), None, 1.0, _ptr(gq),
+                                                  _stream()), 'cbfssm_gp_fullq_lbar_f64')
+            gq = gq * gout
+        return (None,) + _fq_split(gflat, gq, ctx.shapes, need)
+
+
+# ---- conditional() with q_sqrt None or (M, Do) (gp_tf.py:68-88): gp_predict's kernels, with the marginal variances
+# s2 = q_sqrt^2 themselves as the third tensor -- no positivity transform, so q_sqrt^2 below 1e-10 (not a value of
+# softplus + 1e-10) is as good as any other.  d loss / d s2 is the sigma_z^2 section of the reduced slab as it stands.
+
+def _slab_s2_index(lay, M, Do, dev):
+    """positions of (m, d) in the sigma_z^2 section of the slab: an MFMA C-layout image [NBLK][4][64] behind the mean's"""
+    m = torch.arange(M, device=dev).view(M, 1)
+    d = torch.arange(Do, device=dev).view(1, Do)
+    rr = m & 15
+    return lay.NBLK * 256 + ((m >> 4) * 4 + (rr >> 2)) * 64 + 16 * (rr & 3) + d
+
+
+class _GpConditionalDiag(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, Xnew, Z, f, s2, var, ls):
+        M, D, Do = pack.M, pack.D, pack.Do
+        assert tuple(Z.shape) == (M, D) and tuple(f.shape) == (M, Do) and tuple(s2.shape) == (M, Do)
+        assert var.numel() == 1 and ls.numel() == D
+        zp, zm, zv, v, l = [p.detach().reshape(-1) for p in (Z, f, s2, var, ls)]
+        pflat = torch.cat([zp, zm, torch.zeros_like(zv), v, l]).contiguous()      # (the zeta_var_unc entries are a placeholder)
+        cflat = torch.cat([zp, zm, zv, tf_forward(v), tf_forward(l)]).contiguous()
+        _gp_prepare(pack, (Z, f, s2, var, ls), cflat)
+        Xd = Xnew.detach().contiguous()
+        fmean, fvar = pack.predict(Xd)
+        ctx.layout, ctx.buf = pack.layout, pack.buf.clone()
+        ctx.X, ctx.pflat, ctx.cflat = Xd, pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in (Z, f, s2, var, ls))
+        return fmean, fvar
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gmean, gvar):
+        lib = _l.load()
+        lay, buf, X = ctx.layout, ctx.buf, ctx.X
+        need = ctx.needs_input_grad
+        n, dev = X.shape[0], X.device
+        gX = torch.empty_like(X)
+        if n == 0:
+            gp = _gp_split(torch.zeros_like(ctx.pflat), ctx.shapes, need[2:])
+            return (None, gX if need[1] else None) + gp
+        gmean, gvar = gmean.contiguous(), gvar.contiguous()
+        nwg = int(lib.cbfssm_gp_predict_bwd_workgroups(C.byref(lay), n))
+        nwork = int(lib.cbfssm_gp_predict_bwd_work_elems(C.byref(lay), n))
+        if nwg < 1 or nwork < 0:
+            raise _l.CbfssmHipError('cbfssm_gp_predict_bwd_workgroups / _work_elems refused the layout')
+        gpart = torch.empty((nwg + 32) * lay.rev_slab, dtype=torch.float64, device=dev)     # (+ CBFSSM_REDUCE_SPLIT)
+        work = torch.empty(nwork, dtype=torch.float64, device=dev) if nwork else None
+        image = torch.empty(lay.NBLK * lay.NBLK * 256, dtype=torch.float64, device=dev) if lay.rev_stash else None
+        _l.check(lib.cbfssm_gp_predict_bwd_f64(C.byref(lay), _ptr(buf), _ptr(X), n, _ptr(gmean), _ptr(gvar), _ptr(gX),
+                                               _ptr(gpart), _ptr(work), _ptr(image), _stream()), 'cbfssm_gp_predict_bwd_f64')
+        gp = [None] * 5
+        if any(need[2:]):
+            red = torch.empty(lay.rev_slab, dtype=torch.float64, device=dev)
+            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), lay.rev_slab, nwg, _ptr(red), _stream()),
+                     'cbfssm_reduce_partials_f64')
+            if need[2] or need[3] or need[5] or need[6]:
+                gp = list(_gp_split(_gp_tail(lay, buf, red, image, 0.0, ctx.pflat, ctx.cflat), ctx.shapes, need[2:]))
+            if need[4]:
+                M, Do = ctx.shapes[2]
+                gp[2] = red[_slab_s2_index(lay, M, Do, dev)]
+            else:
+                gp[2] = None
+        return (None, gX if need[1] else None) + tuple(gp)
+
+
+def gp_conditional_diag(pack, Xnew, Z, f, s2, variance_unc, lengthscales_unc):
+    """conditional(Xnew, Z, kern, f, q_sqrt) for q_sqrt None (s2 = 0) or (M, Do) (s2 = q_sqrt^2, CONSTRAINED marginal
+    variances) -> (fmean, fvar) with a grad_fn into Xnew, Z, f, s2 and the kernel's two unconstrained tensors."""
+    dev = pack.buf.device
+    args = [torch.as_tensor(p, dtype=torch.float64, device=dev) for p in (Xnew, Z, f, s2, variance_unc, lengthscales_unc)]
+    assert args[0].dim() == 2 and args[0].shape[1] == pack.D
+    return _GpConditionalDiag.apply(pack, *args)
+
+
+def _fq_args(pack, params):
+    if len(params) != 5:
+        raise TypeError('expected the five tensors %s' % ', '.join(GP_FULLQ_PARAM_NAMES))
+    dev = pack.buf.device
+    return [torch.as_tensor(p, dtype=torch.float64, device=dev) for p in params]
+
+
+def gp_predict_fullq(pack, X, *params):
+    """The full-covariance conditional -> (fmean (npts, Do), fvar (npts, Do)) with a grad_fn into X, zeta_pos, zeta_mean,
+    q_sqrt (Do, M, M), variance_unc and lengthscales_unc."""
+    X = torch.as_tensor(X, dtype=torch.float64, device=pack.buf.device)
+    assert X.dim() == 2 and X.shape[1] == pack.D
+    return _GpPredictFullq.apply(pack, X, *_fq_args(pack, params))
+
+
+def gp_prior_kl_fullq(pack, *params):
+    """KL(N(zeta_mean_d, L_d L_d^T) || N(0, K)) summed over the output dimensions, as a 0-d tensor with a grad_fn."""
+    return _GpPriorKlFullq.apply(pack, *_fq_args(pack, params))
 
 
 # ---- the recurrence of one sparse GP: h <- h + gp(h, a_t) + eps_t sqrt(fvar + var_add) over time, one launch ------------

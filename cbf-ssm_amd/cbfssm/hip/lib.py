@@ -37,6 +37,9 @@ SYMBOLS = (
     'cbfssm_rigid_filter_partials', 'cbfssm_rigid_filter_f64', 'cbfssm_rigid_filter_bwd_f64',
     'cbfssm_gru_recog_bwd_in_f64', 'cbfssm_conv_recog_bwd_in_f32', 'cbfssm_half_forward_pass_bwd_in_f64',
     'cbfssm_half_input_grads_f64',
+    'cbfssm_gp_fullq_pack_elems', 'cbfssm_gp_fullq_prepare_f64', 'cbfssm_gp_fullq_kl_f64', 'cbfssm_gp_fullq_bwd_workgroups',
+    'cbfssm_gp_fullq_a2_elems', 'cbfssm_gp_fullq_bwd_work_elems', 'cbfssm_gp_fullq_bwd_f64', 'cbfssm_gp_fullq_wd_work_elems',
+    'cbfssm_gp_fullq_wd_f64', 'cbfssm_gp_fullq_lbar_f64', 'cbfssm_gp_tail_fullq_f64', 'cbfssm_gp_fullq_predict_f64',
 )
 
 
@@ -173,6 +176,23 @@ def load():
         getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]
     lib.cbfssm_gp_predict_bwd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     lib.cbfssm_gp_tail_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, dbl, vp, vp, vp, vp, vp]
+    # full-covariance q(z): every element count is 64-bit
+    lib.cbfssm_gp_fullq_pack_elems.restype = i64
+    lib.cbfssm_gp_fullq_pack_elems.argtypes = [C.POINTER(PackLayout)]
+    for name in ('cbfssm_gp_fullq_bwd_workgroups', 'cbfssm_gp_fullq_a2_elems', 'cbfssm_gp_fullq_bwd_work_elems',
+                 'cbfssm_gp_fullq_wd_work_elems'):
+        getattr(lib, name).restype = i64
+        getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]
+    lib.cbfssm_gp_fullq_prepare_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp]
+    lib.cbfssm_gp_fullq_predict_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, vp, vp, vp]
+    lib.cbfssm_gp_fullq_kl_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, vp, vp, vp]
+    lib.cbfssm_gp_fullq_bwd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cbfssm_gp_fullq_wd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, i64, vp, vp, vp]
+    lib.cbfssm_gp_fullq_lbar_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, dbl, vp, vp]
+    lib.cbfssm_gp_tail_fullq_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, vp, i64, dbl, vp, vp, vp, vp, vp]
+    for name in ('cbfssm_gp_fullq_pack_elems', 'cbfssm_gp_fullq_bwd_workgroups', 'cbfssm_gp_fullq_a2_elems',
+                 'cbfssm_gp_fullq_bwd_work_elems', 'cbfssm_gp_fullq_wd_work_elems'):
+        assert getattr(lib, name).restype is i64, name
     for name in ('cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_bwd_workgroups'):
         getattr(lib, name).restype = i64
         getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]

@@ -8,7 +8,15 @@ stand-alone surface of the same kernels, for callers that hold GP objects rather
     kern.K(X), kern.K(X, X2), kern.Kdiag(X)
     cast_cholesky(mat, jitter=1e-8)                    gp_tf.py:52-65  (float64 whatever the input dtype)
     conditional(Xnew, X, kern, f, q_sqrt, Lm=None)     gp_tf.py:68-100 (q_sqrt None, (M, Do) or (Do, M, M))
-    GPModel(in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var)      gp_tf.py:103-172
+    GPModel(in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var, q_full=False)     gp_tf.py:103-172
+
+Every function here that the reference can differentiate is differentiable.  `conditional` returns tensors with a grad_fn
+when grad is enabled and one of Xnew, X, f, q_sqrt, kern.variance_unc, kern.lengthscales_unc requires it, in all three
+q_sqrt branches: None and (M, Do) through the batch adjoint of GPModel.predict, (Do, M, M) through the full-covariance
+adjoint (cbfssm.hip.autograd.gp_predict_fullq: the S_d A2 product on the f64 MFMA units, d loss / d q_sqrt exactly zero
+above the diagonal).  `GPModel(..., q_full=True)` holds a full-covariance q(z) -- lower-triangular factors `zeta_sqrt`
+(Do, M, M), the zeta_std.ndims == 3 branch of gp_tf.py:150-159 -- and trains with torch.optim through the same kernels;
+`rollout` / `filter` are for the diagonal q(z) only.
 
 GPModel is differentiable: when one of its five leaf tensors (`GPModel.parameters()`) or `Xnew` requires grad, `predict`
 and `prior_kl` return tensors with a grad_fn (cbfssm.hip.autograd.gp_predict / gp_prior_kl: hand-written adjoint kernels,
@@ -112,9 +120,15 @@ def conditional(Xnew, X, kern, f, q_sqrt, Lm=None):
     """GPflow-1.0-style conditional (gp_tf.py:68-100): p(f* | q(f) = N(f, q_sqrt q_sqrt^T)), unwhitened.
     q_sqrt: None, (M, Do) standard deviations, or (Do, M, M) lower-triangular factors.  `Lm` is accepted for signature
     compatibility; the factor is recomputed from (X, kern) on the device (it is what Lm must equal, gp_tf.py:71-72).
-    Returns (fmean (N, Do), fvar (N, Do)).  Evaluation only: the results carry no grad_fn whatever the arguments require
-    (the differentiable surface is GPModel.predict / prior_kl)."""
+    Returns (fmean (N, Do), fvar (N, Do)).  When grad is enabled and Xnew, X, f, q_sqrt, kern.variance_unc or
+    kern.lengthscales_unc requires grad, the results carry a grad_fn (hand-written adjoint kernels in all three branches;
+    the gradient of a (Do, M, M) q_sqrt is exactly zero above the diagonal, whose entries that path never reads).  Without a
+    gradient request the call is evaluation only, the code and the bits it always was: it hands q_sqrt to its kernel as it
+    is, and like the reference's matmul (gp_tf.py:94) that kernel reads the whole matrix, so pass lower-triangular factors."""
     dev = kern.device
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad
+                                       for t in (Xnew, X, f, q_sqrt, kern.variance_unc, kern.lengthscales_unc)):
+        return _conditional_grad(Xnew, X, kern, f, q_sqrt)
     X, Xnew, f = _f64(X, dev), _f64(Xnew, dev), _f64(f, dev)
     M, Do = f.shape
     if q_sqrt is None:
@@ -139,32 +153,80 @@ def conditional(Xnew, X, kern, f, q_sqrt, Lm=None):
     return fmean, fvar
 
 
+def _conditional_grad(Xnew, X, kern, f, q_sqrt):
+    """conditional() under a gradient request: the same three branches through cbfssm.hip.autograd"""
+    from ..hip import autograd as _ag
+    dev = kern.device
+    as64 = lambda t: torch.as_tensor(t, dtype=torch.float64, device=dev)
+    X, Xnew, f = as64(X), as64(Xnew), as64(f)
+    M, Do = f.shape
+    pack = ops.GPPack(M, X.shape[1], Do, dev)
+    if q_sqrt is None or as64(q_sqrt).dim() == 2:
+        if q_sqrt is None:
+            s2 = torch.zeros(M, Do, dtype=torch.float64, device=dev)
+        else:
+            q = as64(q_sqrt)
+            assert q.shape == (M, Do)
+            s2 = q * q                                                       # (its chain rule, 2 q o s2bar, is torch's)
+        out = _ag.gp_conditional_diag(pack, Xnew, X, f, s2, kern.variance_unc, kern.lengthscales_unc)
+    else:
+        q = as64(q_sqrt)
+        if q.dim() != 3:
+            raise ValueError("bad dimension for q_sqrt")
+        assert q.shape == (Do, M, M)
+        out = _ag.gp_predict_fullq(pack, Xnew, X, f, q, kern.variance_unc, kern.lengthscales_unc)
+    if float(pack.scal[_l.SCAL_INFO]) != 0.0:
+        raise InvalidArgumentError('Cholesky decomposition was not successful: leading minor %d of K(X) + 1e-8 I is not '
+                                   'positive definite' % int(pack.scal[_l.SCAL_INFO]))
+    return out
+
+
 class GPModel:
     """Sparse GP with diagonal q(z) (gp_tf.py:103-172): inducing inputs / means drawn as the reference draws them
     (unseeded unless `seed` is given), `predict(Xnew)` and `prior_kl()` on the device.  The five tensors of `parameters()`
     are leaves: set `requires_grad_()` on them (or hand `predict` an `Xnew` that requires grad) and both calls are
-    differentiable; see the module docstring."""
+    differentiable; see the module docstring.
+
+    q_full=True: a full-covariance q(z_d) = N(zeta_mean[:, d], L_d L_d^T) per output dimension (the zeta_std.ndims == 3
+    branch of gp_tf.py:150-159).  The third leaf is then `zeta_sqrt` (Do, M, M), unconstrained, initialised to
+    sqrt(zeta_var) I; only its lower triangle is read and its gradient above the diagonal is exactly zero.  `zeta_std`
+    returns the factors L_d, `zeta_var` the marginal variances diag(L_d L_d^T) as (M, Do).  `rollout` and `filter` raise
+    ValueError on such a model."""
 
     def __init__(self, in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var, dtype='float64',
-                 device=None, seed=None):
+                 device=None, seed=None, q_full=False):
         self.in_dim, self.out_dim, self.num_points, self.dtype = in_dim, out_dim, num_points, dtype
         rng = np.random.default_rng(seed)
         dev = _device(device)
         self.zeta_pos = torch.tensor(rng.uniform(-zeta_pos, zeta_pos, size=(num_points, in_dim)), device=dev)   # :112-115
         self.zeta_mean = torch.tensor(zeta_mean * rng.random((num_points, out_dim)), device=dev)                 # :117-118
-        self.zeta_var_unc = torch.tensor(backward(zeta_var * np.ones((num_points, out_dim))), device=dev)       # :120-121
+        self.q_full = bool(q_full)
+        if self.q_full:
+            eye = np.sqrt(zeta_var) * np.eye(num_points)
+            self.zeta_sqrt = torch.tensor(np.broadcast_to(eye, (out_dim, num_points, num_points)).copy(), device=dev)
+        else:
+            self.zeta_var_unc = torch.tensor(backward(zeta_var * np.ones((num_points, out_dim))), device=dev)   # :120-121
         self.kern = RBF(gp_var, np.asarray([gp_len] * in_dim, dtype=np.float64), device=dev)                     # :125-127
         self._pack = ops.GPPack(num_points, in_dim, out_dim, dev)
 
     @property
     def zeta_var(self):
+        if self.q_full:
+            L = self.zeta_std
+            return (L * L).sum(dim=2).t().contiguous()                       # diag(L_d L_d^T): row sums of squares
         return forward(self.zeta_var_unc)
 
     @property
     def zeta_std(self):
+        if self.q_full:
+            return torch.tril(self.zeta_sqrt.detach())                       # what gp_tf.py:153 reads
         return torch.sqrt(self.zeta_var)
 
     def _prepared(self):
+        if self.q_full:                                                      # (zeta_var = 0: cbfssm_gp_predict_fullq_f64's pack)
+            self._pack.prepare(self.zeta_pos, self.kern.lengthscales, self.kern.variance, self.zeta_mean,
+                               torch.zeros_like(self.zeta_mean))
+            return self._pack
         self._pack.prepare(self.zeta_pos, self.kern.lengthscales, self.kern.variance, self.zeta_mean, self.zeta_var)
         return self._pack
 
@@ -173,19 +235,41 @@ class GPModel:
         return self._prepared().L.clone()                                                                        # :129-130
 
     def parameters(self):
-        """The five trainable leaves, in the order of cbfssm.hip.autograd.GP_PARAM_NAMES."""
+        """The five trainable leaves, in the order of cbfssm.hip.autograd.GP_PARAM_NAMES (q_full: GP_FULLQ_PARAM_NAMES)."""
+        if self.q_full:
+            return [self.zeta_pos, self.zeta_mean, self.zeta_sqrt, self.kern.variance_unc, self.kern.lengthscales_unc]
         return [self.zeta_pos, self.zeta_mean, self.zeta_var_unc, self.kern.variance_unc, self.kern.lengthscales_unc]
 
     def _wants_grad(self, *more):
         return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in self.parameters() + list(more))
 
+    def _no_full_q(self, what):
+        if self.q_full:
+            raise ValueError('GPModel.%s runs a diagonal q(z) only: this model was built with q_full=True (use predict / '
+                             'prior_kl)' % what)
+
     def predict(self, Xnew):
+        if self.q_full:
+            return self._predict_full(Xnew)
         if self._wants_grad(Xnew):
             from ..hip import autograd as _ag
             return _ag.gp_predict(self._pack, Xnew, *self.parameters())
         return self._prepared().predict(Xnew)                                                                    # :132-161
 
+    def _predict_full(self, Xnew):                                                                               # :150-159
+        from ..hip import autograd as _ag
+        if self._wants_grad(Xnew):
+            return _ag.gp_predict_fullq(self._pack, Xnew, *self.parameters())
+        Xnew = _f64(Xnew, self.zeta_pos.device).contiguous()
+        pack = self._prepared() if Xnew.shape[0] else self._pack                 # (nothing runs without a point)
+        return _ag.gp_fullq_eval(pack, Xnew, self.zeta_sqrt, self.zeta_mean)
+
     def prior_kl(self):
+        if self.q_full:
+            from ..hip import autograd as _ag
+            if self._wants_grad():
+                return _ag.gp_prior_kl_fullq(self._pack, *self.parameters())
+            return _ag.gp_fullq_eval(self._prepared(), None, self.zeta_sqrt, self.zeta_mean)
         if self._wants_grad():
             from ..hip import autograd as _ag
             return _ag.gp_prior_kl(self._pack, *self.parameters())
@@ -204,6 +288,7 @@ class GPModel:
         var_add (out_dim) constrained values or None.  Returns (traj (T, N, out_dim), entropy ()).  When a leaf, h0, a or
         var_add requires grad both results carry a grad_fn (cbfssm.hip.autograd.gp_rollout; eps gets no gradient);
         otherwise the forward kernel runs alone and keeps nothing for an adjoint."""
+        self._no_full_q('rollout')
         from ..hip import autograd as _ag
         if self._wants_grad(h0, a, var_add):
             return _ag.gp_rollout(self._pack, h0, a, eps, var_add, *self.parameters(), reverse=reverse)
@@ -227,6 +312,7 @@ class GPModel:
         there, it is never read into a result.  Returns (traj (T, N, out_dim), kl ()).  When a leaf, h0, a, ytilde, var_x or
         var_y requires grad both results carry a grad_fn (cbfssm.hip.autograd.gp_filter; eps, cond and k_factor get no
         gradient); otherwise the forward kernel runs alone and keeps nothing for an adjoint."""
+        self._no_full_q('filter')
         from ..hip import autograd as _ag
         if self._wants_grad(h0, a, ytilde, var_x, var_y):
             return _ag.gp_filter(self._pack, h0, a, ytilde, eps, var_x, var_y, *self.parameters(), cond=cond,

@@ -48,6 +48,8 @@ struct GpTail {
                               // C A2^T); either way only the symmetric part of G enters
     double klw;               // weight of the prior-KL terms (gp_tf.py:163-172): 1 in a train step, the caller's in cbfssm_gp_tail_f64
     int nodata;               // 1: there is no slab (cbfssm_gp_tail_f64 with red_slab = NULL): the data terms read as zero
+    const double* Ssum;       // full-covariance q(z) (cbfssm_gp_tail_fullq_f64): [M][M] sum_d S_d, which takes the place of
+                              // diag(sum_d zvar) in the prior-KL part; zvar is then not read and g_s2 is written as zero.  NULL: diagonal q(z)
 };
 
 struct TailArgs {
@@ -115,6 +117,7 @@ __device__ __forceinline__ double g_elem(const GpTail& p, int k, int j)
     if (p.Kkl) return v;                                  // (PR-SSM: the prior-KL part goes through Kkl, tail_gemm<3>)
     double dot = 0.0;
     for (int d = 0; d < p.Do; ++d) dot = fma(p.zmean[k * p.Do + d], p.zmean[j * p.Do + d], dot);
+    if (p.Ssum) return v + p.klw * (0.5 * (dot + p.Ssum[int64_t(k) * p.M + j]));
     if (k == j)
         for (int d = 0; d < p.Do; ++d) dot += p.zvar[k * p.Do + d];
     return v + p.klw * (0.5 * dot);
@@ -303,6 +306,7 @@ __global__ __launch_bounds__(256) void tail_finish(TailArgs a)
         const int i = idx / Do, d = idx - i * Do;
         const double gm0 = nd ? 0.0 : c_image(gMu, 1, i, d), gs0 = nd ? 0.0 : c_image(gS2, 1, i, d);
         p.g_mu[idx] = gm0 + p.klw * KM[idx];
+        if (p.Ssum) { p.g_s2[idx] = 0.0; continue; }      // (the factors' adjoint is cbfssm_gp_fullq_lbar_f64)
         const double gs2 = gs0 + p.klw * 0.5 * ((p.Kkl ? p.Kkl : p.Kinv)[int64_t(i) * M + i] - 1.0 / p.zvar[idx]);
         p.g_s2[idx] = gs2 * sigmoid(p.zvar_unc[idx]);
     }
@@ -388,7 +392,8 @@ namespace cbfssm {
 // vectors end behind the lengthscales (no var_x / var_y) and `slab` may be NULL (the prior-KL terms alone).
 static int one_gp_tail(const cbfssm_pack_layout* L, const double* pack, const double* pack_kl, int shared_ls, const double* slab,
                        const double* gB_dense, int64_t gB_ld, int g_mode, double klw, int dim_y, const double* pflat,
-                       const double* cflat, double* work, double* gflat, void* stream, const char* what)
+                       const double* cflat, double* work, double* gflat, void* stream, const char* what,
+                       const double* Ssum = nullptr)
 {
     TailArgs a;
     memset(&a, 0, sizeof(a));
@@ -406,6 +411,7 @@ static int one_gp_tail(const cbfssm_pack_layout* L, const double* pack, const do
     p.Kkl = pack_kl ? pack_kl + L->Kinv : nullptr;
     p.shared_ls = shared_ls ? 1 : 0;
     p.klw = klw; p.nodata = slab ? 0 : 1;
+    p.Ssum = Ssum;
     // flat layout: zeta_pos [M][D] | zeta_mean [M][Do] | zeta_var(_unc) [M][Do] | variance(_unc) [1] | lengthscales(_unc)
     // [D or 1] | var_x(_unc) [Do] | var_y(_unc) [dim_y]
     const int64_t o1 = int64_t(M) * D, o2 = o1 + int64_t(M) * Do, o3 = o2 + int64_t(M) * Do, o4 = o3 + 1,
@@ -582,6 +588,23 @@ int cbfssm_gp_tail_f64(const cbfssm_pack_layout* L, const double* pack, const do
     if (!red_slab && gB_dense) return fail(-1, "a K^-1 adjoint without a slab");
     return one_gp_tail(L, pack, nullptr, 0, red_slab, gB_dense, gB_ld, 0, kl_weight, 0, pflat, cflat, work, gflat, stream,
                        "gp tail launch failed");
+}
+
+int cbfssm_gp_tail_fullq_f64(const cbfssm_pack_layout* L, const double* pack, const double* qpack, const double* red_slab,
+                             const double* gB_dense, int64_t gB_ld, double kl_weight, const double* pflat, const double* cflat,
+                             double* work, double* gflat, void* stream)
+{
+    if (!L || !pack || !qpack || !pflat || !cflat || !work || !gflat) return fail(-1, "null pointer");
+    if (L->rev_slab <= 0) return fail(-3, "no adjoint slab for M=%d", L->M);
+    if (L->M < 1 || L->M > 320 || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT)
+        return fail(-3, "tail kernel limits: M <= 320, D <= 24, Do <= %d", CBFSSM_MAX_DOUT);
+    if (red_slab && (L->rev_stash != 0) != (gB_dense != nullptr))
+        return fail(-1, "the dense K^-1 adjoint is required exactly in stash mode");
+    if (!red_slab && gB_dense) return fail(-1, "a K^-1 adjoint without a slab");
+    // sum_d S_d sits behind the operand images and the dense S_d of the q pack (cbfssm_gp_fullq_pack_elems)
+    const double* Ssum = qpack + int64_t(L->Do) * L->NBLK * L->KS * 64 + int64_t(L->Do) * L->M * L->M;
+    return one_gp_tail(L, pack, nullptr, 0, red_slab, gB_dense, gB_ld, 0, kl_weight, 0, pflat, cflat, work, gflat, stream,
+                       "gp tail (full q) launch failed", Ssum);
 }
 
 int cbfssm_data_tail_f64(const cbfssm_problem* p, const double* var_y, const double* ll_part, const double* out8, double cL,

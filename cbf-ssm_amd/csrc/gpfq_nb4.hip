@@ -1,0 +1,2 @@
+#include "cbfssm_gp_fullq.hpp"
+CBF_GPFQ_INSTANTIATE(4)

@@ -182,6 +182,61 @@ int cbfssm_gp_tail_f64(const cbfssm_pack_layout* layout, const double* pack, con
                        void* stream);
 
 /*
+ * ---- full-covariance q(z), differentiable: conditional() with q_sqrt of shape (Do, M, M) (gp_tf.py:68-100, the
+ * q_sqrt.ndims == 3 branch at :89-98) and GPModel.predict with zeta_std.ndims == 3 (gp_tf.py:150-159), differentiated as
+ * tf.gradients does.  L_d = tril(q_sqrt[d]) (entries above the diagonal are never read), S_d = L_d L_d^T, unwhitened:
+ *
+ *   fvar[n][d] = sigma^2 - k_n^T a_n + a_n^T S_d a_n,  a_n = K^-1 k_n                                  gp_tf.py:79,91-98
+ *   prior_kl   = 0.5 sum_d [ tr(K^-1 S_d) + f_d^T K^-1 f_d - M + log det K - sum_i log L_d[i][i]^2 ]   gp_tf.py:163-172 with
+ *                                                                                   MultivariateNormalTriL for q
+ *
+ * The pack is prepared with f as zeta_mean; no call below reads its zeta_var.
+ *
+ * cbfssm_gp_fullq_prepare_f64 (gp_tf.py:91-93): q_sqrt (Do, M, M) -> qpack (cbfssm_gp_fullq_pack_elems doubles): the MFMA
+ *   operand images of S_d, S_d dense, and sum_d S_d.  Once per call of the functions below.
+ * cbfssm_gp_fullq_predict_f64 (gp_tf.py:76-98): the forward on the f64 MFMA units, X (npts, D) -> fmean, fvar (npts, Do); A2 in
+ *   the form layout->gp_form asks for, then per output dimension S_d A2 from the qpack's images and the column sums
+ *   a^T S_d a.  Only the lower triangle of q_sqrt enters.
+ * cbfssm_gp_fullq_kl_f64 (gp_tf.py:163-172): zeta_mean (M, Do) -> kl (ONE double on the device).
+ * cbfssm_gp_fullq_bwd_f64 (gp_tf.py:76-98 differentiated): the batch adjoint, arguments and results as
+ *   cbfssm_gp_predict_bwd_f64 (gX, gpart with cbfssm_gp_fullq_bwd_workgroups slabs and room for CBFSSM_REDUCE_SPLIT more,
+ *   the sigma_z^2 section zero; work of cbfssm_gp_fullq_bwd_work_elems doubles and gB_image above M = 112), plus
+ *   a2_image (cbfssm_gp_fullq_a2_elems doubles): A2 = K^-1 k of every 16-point block, for cbfssm_gp_fullq_wd_f64.
+ * cbfssm_gp_fullq_wd_f64 (gp_tf.py:91-98 differentiated): a2_image, gvar (npts, Do) -> W (Do, M, M),
+ *   W_d = sum_n gvar[n][d] a_n a_n^T = d loss / d S_d, exactly symmetric; work: cbfssm_gp_fullq_wd_work_elems doubles
+ *   (partial tiles of up to 8 slices of the points, summed in a fixed order).
+ * cbfssm_gp_fullq_lbar_f64 (gp_tf.py:91-98,163-172 differentiated): gq (Do, M, M) = tril((2 W_d + kl_weight K^-1) L_d)
+ *   - kl_weight diag(1 / L_d[i][i]), exactly zero above the diagonal.  W NULL: the prior-KL part alone; pack NULL: the
+ *   data part alone.
+ * cbfssm_gp_tail_fullq_f64 (gp_tf.py:33-65,129-130,163-172 differentiated): cbfssm_gp_tail_f64 with the prior-KL part of
+ *   the K^-1 adjoint taken from sum_d S_d; the flat vectors keep their order, the zeta_var entries of pflat / cflat are
+ *   not read and those of gflat are written as zero.
+ * No atomics, no host synchronisation, every output entry has one writer, two calls are bitwise identical; nothing is
+ * launched at npts = 0.  Limits as cbfssm_gp_predict_f64 (M <= 320, D <= 24, Do <= 16), else -3 before any launch; NULL
+ * pointers -1.  The counts are host arithmetic in 64 bits and return -1 for a bad layout or npts < 0.
+ */
+int64_t cbfssm_gp_fullq_pack_elems(const cbfssm_pack_layout* layout);
+int cbfssm_gp_fullq_prepare_f64(const cbfssm_pack_layout* layout, const double* q_sqrt, double* qpack, void* stream);
+int cbfssm_gp_fullq_predict_f64(const cbfssm_pack_layout* layout, const double* pack, const double* qpack, const double* X,
+                                int64_t npts, double* fmean, double* fvar, void* stream);
+int cbfssm_gp_fullq_kl_f64(const cbfssm_pack_layout* layout, const double* pack, const double* q_sqrt, const double* qpack,
+                           const double* zeta_mean, double* kl, void* stream);
+int64_t cbfssm_gp_fullq_bwd_workgroups(const cbfssm_pack_layout* layout, int64_t npts);
+int64_t cbfssm_gp_fullq_a2_elems(const cbfssm_pack_layout* layout, int64_t npts);
+int64_t cbfssm_gp_fullq_bwd_work_elems(const cbfssm_pack_layout* layout, int64_t npts);
+int cbfssm_gp_fullq_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* qpack, const double* X,
+                            int64_t npts, const double* gmean, const double* gvar, double* gX, double* gpart,
+                            double* a2_image, double* work, double* gB_image, void* stream);
+int64_t cbfssm_gp_fullq_wd_work_elems(const cbfssm_pack_layout* layout, int64_t npts);
+int cbfssm_gp_fullq_wd_f64(const cbfssm_pack_layout* layout, const double* a2_image, const double* gvar, int64_t npts,
+                           double* work, double* W, void* stream);
+int cbfssm_gp_fullq_lbar_f64(const cbfssm_pack_layout* layout, const double* pack, const double* q_sqrt, const double* W,
+                             double kl_weight, double* gq, void* stream);
+int cbfssm_gp_tail_fullq_f64(const cbfssm_pack_layout* layout, const double* pack, const double* qpack, const double* red_slab,
+                             const double* gB_dense, int64_t gB_ld, double kl_weight, const double* pflat, const double* cflat,
+                             double* work, double* gflat, void* stream);
+
+/*
  * ---- differentiable GP rollout: the time loop of ONE sparse GP with per-chain inputs, and its adjoint.
  * Replaces the loop bodies of Voliro's recognition run (cbfssm/model/voliro.py:139-186: one run from h = 0, backwards in
  * time, GP input (h, u_t, y_t) with a per-particle u_t) and of the free-running transition of a trained CBF-SSM
