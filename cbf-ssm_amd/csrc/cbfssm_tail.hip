@@ -145,7 +145,9 @@ __global__ __launch_bounds__(256) void tail_gemm(TailArgs a)
             double av = 0.0;
             if (i < M && k0 + tx < M) {
                 const int k = k0 + tx;
-                av = km ? (p.Kkl ? p.Kkl : p.Kinv)[int64_t(i) * M + k] : -0.5 * (p.G2[int64_t(i) * M + k] + p.G2[int64_t(k) * M + i]);
+                // (Ws without its diagonal: K_ii does not depend on z, see tail_finish)
+                av = km ? (p.Kkl ? p.Kkl : p.Kinv)[int64_t(i) * M + k]
+                        : (k == i ? 0.0 : -0.5 * (p.G2[int64_t(i) * M + k] + p.G2[int64_t(k) * M + i]));
             }
             As[ty][tx] = av;
             double bv = 0.0;
@@ -260,7 +262,8 @@ __global__ __launch_bounds__(256) void tail_finish(TailArgs a)
     double tot = 0.0;
     for (int i = wv; i < M; i += NT / 64) {              // one wave per row: lanes over the columns
         double s = 0.0;
-        for (int j = l; j < M; j += 64) s += G2[int64_t(i) * M + j] + G2[int64_t(j) * M + i];
+        for (int j = l; j < M; j += 64)
+            if (j != i) s += G2[int64_t(i) * M + j] + G2[int64_t(j) * M + i];
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
         if (l == 0) wsrow[i] = -0.5 * s;
     }
@@ -269,6 +272,9 @@ __global__ __launch_bounds__(256) void tail_finish(TailArgs a)
     __syncthreads();
 
     // Z~bar = Ebar x~^T - z~ o rowsum(Ebar) + 2 (rowsum(Ws) o z~ - Ws z~);   zbar = Z~bar / ls
+    // Row i of the last bracket is sum_j Ws_ij (z~_i - z~_j): the j = i term is zero, so both sums leave the diagonal of Ws
+    // out (wsrow above, tail_gemm<2>).  Kept, it cancels between the two only up to rounding, and at M = 1, where K_mm is a
+    // scalar that does not depend on z, the prior-KL gradient of zeta_pos and of the lengthscales came out as 1e-17, not 0.
     // lengthscales: -(colsum(Z~bar o z~) + inputs' part) / ls; thread j < D walks its column (fixed order)
     for (int idx = tid; idx < M * D; idx += NT) {
         const int i = idx / D, j = idx - i * D;

@@ -32,6 +32,9 @@ no gradient tensor's largest entry is below 7.9e-3.  D = 4 is not used at M >= 1
 cond 4e6 and the codings then agree on the trajectory to 2.9e-9 only.
 
 To extend: a new tile height, input width or trim makes test_gp_tile_grid_cpu fail until ROWS has a row that reaches it.
+
+The same rows run the GP filter loop and full-covariance q(z), whose kernels are copies of these with one phase replaced:
+tests/gp_filter_fullq_grid.py derives their cases from ROWS and reads their launchers.
 """
 import functools
 import os

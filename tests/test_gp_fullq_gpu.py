@@ -40,14 +40,14 @@ def _check_upper_zero(g, M):
     assert np.all(g[:, upper] == 0.0), 'd/dq above the diagonal is not exactly zero'
 
 
-def _abi(M, D, Do, npts, p, X, Wm, Wv, kl_weight, data=True):
-    """the C calls in the order cbfssm.hip.autograd makes them; buffers poisoned with NaN.
+def _abi(M, D, Do, npts, p, X, Wm, Wv, kl_weight, data=True, form='dense'):
+    """the C calls in the order cbfssm.hip.autograd makes them; buffers poisoned with NaN.  form: 'dense' or 'tri', the pack's.
     returns (grads dict by PARAMS, gX, fmean, fvar, kl, everything concatenated for the bitwise comparison)"""
     from cbfssm.hip import lib as _l, ops
     from cbfssm.hip.ops import _ptr, _stream
     lib = _l.load()
     nan = float('nan')
-    pack = ops.GPPack(M, D, Do, torch.device(DEV), form_mode='dense')
+    pack = ops.GPPack(M, D, Do, torch.device(DEV), form_mode=form)
     pt = {k: _dev(p[k]) for k in PARAMS}
     var, ls = ops.tf_forward(pt['variance_unc']), ops.tf_forward(pt['lengthscales_unc'])
     hole = torch.zeros(M * Do, dtype=torch.float64, device=DEV)
