@@ -37,7 +37,10 @@ for tag, slab, nwg, nstep_total in (('fwd-adjoint', eng.red[:eng.slab_f], ws.n_f
             print('     %-32s compute %5.1f%%  barrier-wait %5.1f%%' % (names[i], 100 * c[i] / tot, 100 * wt[i] / tot))
         if wname == 'wave0':
             marks = small[128:140]
-            mn = ['C loop (only without saved A2)', '-', 'B rest (after the input loads)', 'D epilogue adjoint (next step)', '-', 'E whole',
+            # (eight-wave tiles: mark 8 is only the store of Ebar to the LDS tile, Zbar~ runs in the dealt waves behind
+            #  barrier 5 -- mark 4, recorded in a -DCBF_STAMP_MARKS_LAST build)
+            mn = ['C loop (only without saved A2)', '-', 'B rest (after the input loads)', 'D epilogue adjoint (next step)',
+                  'G window: dealt gZ', 'E whole',
                   'F loop(25)', 'F xp(8)', 'F transpose+gZ(8)', 'B saved rows -> LDS', 'B next inputs issued', 'loop back edge']
             if os.environ.get('MARKS_LAST'):
                 print('        (sub-phase marks of the second recorded wave: -DCBF_STAMP_MARKS_LAST build)')
