@@ -161,7 +161,9 @@ __global__ __launch_bounds__(PREP_NT) void prepare_kernel(PrepArgs2 aa)
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * ib + g + 4 * r, k = 16 * kb + nl;
             if (i < M && k < M) {
-                const double d2 = -2.0 * dot[r] + Xs[i] + Xs[k];              // gp_tf.py:37-38, no clamp
+                // gp_tf.py:37-38, no clamp.  The two norms are added first: (-2 dot + |x_i|^2) + |x_k|^2 rounds
+                // differently at (i, k) and (k, i), and K_mm has to be symmetric to the last bit
+                const double d2 = -2.0 * dot[r] + (Xs[i] + Xs[k]);
                 const double kv = var * exp(-0.5 * d2);                       // gp_tf.py:49
                 a.Kmm[i * M + k] = kv;
                 Wm[i * LD + k] = (k < i) ? kv : ((k == i) ? kv + a.jitter : 0.0);   // gp_tf.py:53
@@ -1098,6 +1100,18 @@ int cbfssm_gp_prepare2_f64(const cbfssm_pack_layout* L0, const double* Z0, const
     if (rc) return rc;
     rc = fill_prep(aa.g[1], L1, Z1, ls1, var1, zmean1, zvar1, jitter, pack1);
     if (rc) return rc;
+    // The kernel template (working matrix in LDS or in the pack's `work` section) is one choice per launch.  A pack with
+    // M <= PREP_LDS_MAX_M has no `work` section (gmat = null), so when exactly one of the two needs the global-memory
+    // form each gets its own single-GP launch, in order on the stream.
+    if ((L0->M > PREP_LDS_MAX_M) != (L1->M > PREP_LDS_MAX_M)) {
+        PrepArgs2 a1;
+        memset(&a1, 0, sizeof(a1));
+        a1.g[0] = aa.g[1];
+        memset(&aa.g[1], 0, sizeof(aa.g[1]));
+        rc = launch_prepare(aa, 1, L0->M, (hipStream_t)stream);
+        if (rc) return rc;
+        return launch_prepare(a1, 1, L1->M, (hipStream_t)stream);
+    }
     return launch_prepare(aa, 2, L0->M > L1->M ? L0->M : L1->M, (hipStream_t)stream);
 }
 

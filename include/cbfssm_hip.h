@@ -115,7 +115,11 @@ int cbfssm_gp_prepare_f64(const cbfssm_pack_layout* layout, const double* Z, con
                           const double* variance, const double* zeta_mean, const double* zeta_var,
                           double jitter, double* pack, void* stream);
 
-/* The same for two GPModels in one launch (gp_f and gp_b of CBFSSM._setup_vars, cbfssm.py:30-48): one workgroup each. */
+/* The same for two GPModels in one launch (gp_f and gp_b of CBFSSM._setup_vars, cbfssm.py:30-48): one workgroup each.
+ * The two layouts need not agree in M, D or Do.  The factorisation keeps its working matrix in LDS up to M = 140 and in
+ * the pack's `work` section above; when exactly one of the two M exceeds 140 the call issues two single-GP launches on
+ * `stream` (as two cbfssm_gp_prepare_f64 calls would), otherwise the one two-workgroup launch.  Either way each pack is
+ * bitwise what cbfssm_gp_prepare_f64 writes for the same inputs. */
 int cbfssm_gp_prepare2_f64(const cbfssm_pack_layout* layout0, const double* Z0, const double* lengthscales0,
                            const double* variance0, const double* zeta_mean0, const double* zeta_var0, double* pack0,
                            const cbfssm_pack_layout* layout1, const double* Z1, const double* lengthscales1,
