@@ -2,7 +2,8 @@
 functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down; `gp_predict_fullq`, `gp_prior_kl_fullq` with a
 full-covariance q(z), `gp_conditional_diag` behind `gp_tf.conditional`), its recurrence over time (`gp_rollout`), the same
 recurrence with a masked Gaussian filter update per step (`gp_filter`) and the rigid-body filter loop of the Voliro model
-(`rigid_filter`, at the end).
+(`rigid_filter`, at the end).  `gp_linearize_eval` is evaluation only: the Jacobians of the GP mean and variance with respect
+to the inputs, all output dimensions in one launch.
 
 The CBF-SSM loss:
 
@@ -615,6 +616,41 @@ def gp_rollout_eval(pack, h0, a, eps, var_add, reverse=False):
         traj, _, ent = _rollout_forward(pack.layout, pack.buf, h0.contiguous(), a.contiguous() if a is not None else None,
                                         eps.contiguous(), var_add.contiguous() if var_add is not None else None, reverse, False)
     return traj, ent
+
+
+# ---- the local linear model of one sparse GP: d fmean / d X and d fvar / d X at a batch of points -------------------------
+#
+#     fmean, fvar, dmean, dvar = gp_linearize_eval(pack, X, variance=True)
+#
+# what the reference gets from tf.gradients(fmean[:, d], Xnew) / tf.gradients(fvar[:, d], Xnew) per output dimension d
+# through gp_tf.py:132-161, as one launch for all dimensions (cbfssm_gp_linearize_f64: per 16 points one kernel tile,
+# 1 + Do products with K^-1 and the (Z / lengthscale)^T products) instead of 2 Do backward calls through gp_predict.
+
+def gp_linearize_eval(pack, X, variance=True):
+    """(fmean (npts, Do), fvar (npts, Do), dmean (npts, Do, D), dvar (npts, Do, D) or None) on a pack that is already
+    prepared: dmean[n, d, i] = d fmean[n, d] / d X[n, i], dvar the same of fvar.  variance=False leaves the variance
+    Jacobian (and its K^-1 product per output dimension) out; dmean and fmean are bitwise those of the full call.
+    Evaluation only: no grad_fn, no host synchronisation, nothing is launched without a point."""
+    lib = _l.load()
+    lay, dev = pack.layout, pack.buf.device
+    X = torch.as_tensor(X, dtype=torch.float64, device=dev)
+    assert X.dim() == 2 and X.shape[1] == pack.D, 'X (npts, D)'
+    n, D, Do = X.shape[0], pack.D, pack.Do
+    with torch.no_grad():
+        X = X.detach().contiguous()
+        fmean = torch.empty(n, Do, dtype=torch.float64, device=dev)
+        fvar = torch.empty_like(fmean)
+        dmean = torch.empty(n, Do, D, dtype=torch.float64, device=dev)
+        dvar = torch.empty_like(dmean) if variance else None
+        if n == 0:
+            return fmean, fvar, dmean, dvar
+        nwork = int(lib.cbfssm_gp_linearize_work_elems(C.byref(lay)))
+        if nwork < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_linearize_work_elems refused the layout')
+        work = torch.empty(nwork, dtype=torch.float64, device=dev)
+        _l.check(lib.cbfssm_gp_linearize_f64(C.byref(lay), _ptr(pack.buf), _ptr(X), n, _ptr(fmean), _ptr(fvar), _ptr(dmean),
+                                             _ptr(dvar), _ptr(work), _stream()), 'cbfssm_gp_linearize_f64')
+    return fmean, fvar, dmean, dvar
 
 
 # ---- the filter loop of one sparse GP: the rollout with a Gaussian filter update per step and chain behind a mask --------

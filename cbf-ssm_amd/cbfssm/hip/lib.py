@@ -40,6 +40,7 @@ SYMBOLS = (
     'cbfssm_gp_fullq_pack_elems', 'cbfssm_gp_fullq_prepare_f64', 'cbfssm_gp_fullq_kl_f64', 'cbfssm_gp_fullq_bwd_workgroups',
     'cbfssm_gp_fullq_a2_elems', 'cbfssm_gp_fullq_bwd_work_elems', 'cbfssm_gp_fullq_bwd_f64', 'cbfssm_gp_fullq_wd_work_elems',
     'cbfssm_gp_fullq_wd_f64', 'cbfssm_gp_fullq_lbar_f64', 'cbfssm_gp_tail_fullq_f64', 'cbfssm_gp_fullq_predict_f64',
+    'cbfssm_gp_linearize_work_elems', 'cbfssm_gp_linearize_f64',
 )
 
 
@@ -193,6 +194,9 @@ def load():
     for name in ('cbfssm_gp_fullq_pack_elems', 'cbfssm_gp_fullq_bwd_workgroups', 'cbfssm_gp_fullq_a2_elems',
                  'cbfssm_gp_fullq_bwd_work_elems', 'cbfssm_gp_fullq_wd_work_elems'):
         assert getattr(lib, name).restype is i64, name
+    lib.cbfssm_gp_linearize_work_elems.restype = i64
+    lib.cbfssm_gp_linearize_work_elems.argtypes = [C.POINTER(PackLayout)]
+    lib.cbfssm_gp_linearize_f64.argtypes = [C.POINTER(PackLayout), vp, vp, i64, vp, vp, vp, vp, vp, vp]
     for name in ('cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_bwd_workgroups'):
         getattr(lib, name).restype = i64
         getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]

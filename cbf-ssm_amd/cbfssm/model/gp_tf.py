@@ -24,6 +24,12 @@ no tensor-library fallback), so a model built around a sparse GP -- the referenc
 physics term (cbfssm/model/voliro.py:106-123) -- trains with torch.optim.  Without a gradient request both are the
 evaluation-only calls they always were.  `GPModel.rollout` (not in the reference) runs the GP's recurrence over time with
 per-chain inputs as one fused launch, differentiable in the same way.
+
+`GPModel.linearize(Xnew)` hands out the local linear model of the learned function: fmean, fvar and their Jacobians with
+respect to Xnew for all output dimensions in one launch -- what the reference gets from tf.gradients(fmean[:, d], Xnew) per
+output dimension through gp_tf.py:132-161 -- and `GPModel.transition_jacobians(h, a)` the matrices A = d m / d h,
+B = d m / d a of the recurrence m = h + fmean(concat(h, a)) that `rollout` and `filter` run (EKF-style filtering, iLQR / MPC
+around a learned transition).  Both are evaluation only and for the diagonal q(z).
 """
 import ctypes as C
 import numpy as np
@@ -319,3 +325,47 @@ class GPModel:
                                  k_factor=k_factor, reverse=reverse)
         pack = self._prepared() if torch.as_tensor(eps).numel() else self._pack      # (nothing runs without a chain or a step)
         return _ag.gp_filter_eval(pack, h0, a, ytilde, eps, var_x, var_y, cond=cond, k_factor=k_factor, reverse=reverse)
+
+    def linearize(self, Xnew, variance=True):
+        """An addition to the reference's surface, which takes tf.gradients(fmean[:, d], Xnew) per output dimension d
+        through gp_tf.py:132-161: the local linear model of the GP at every row of Xnew (N, in_dim), as one launch,
+
+            fmean, fvar (N, out_dim) = predict(Xnew)
+            dmean[n, d, i] = d fmean[n, d] / d Xnew[n, i],   dvar[n, d, i] = d fvar[n, d] / d Xnew[n, i]    (N, out_dim, in_dim)
+
+        Returns (fmean, fvar, dmean, dvar); variance=False leaves the variance Jacobian out (dvar is None, the K^-1 product
+        per output dimension it needs is not done; the other three results are bitwise the same).  Evaluation only: the
+        results carry no grad_fn whatever the leaves or Xnew ask for -- differentiating a Jacobian is not offered.  Raises
+        ValueError on a q_full=True model."""
+        self._no_full_q('linearize')
+        from ..hip import autograd as _ag
+        Xnew = _f64(Xnew, self.zeta_pos.device)
+        pack = self._prepared() if Xnew.shape[0] else self._pack                 # (nothing runs without a point)
+        return _ag.gp_linearize_eval(pack, Xnew, variance=variance)
+
+    def transition_jacobians(self, h, a=None):
+        """The local linear model of the recurrence `rollout` and `filter` run, m = h + fmean(concat(h, a)):
+
+            A[n] = d m[n] / d h[n] = I + dmean[n, :, :out_dim]   (N, out_dim, out_dim)
+            B[n] = d m[n] / d a[n] = dmean[n, :, out_dim:]        (N, out_dim, in_dim - out_dim)
+
+        h (N, out_dim), a (N, in_dim - out_dim) or None when the GP takes the state alone.  Returns (A, B); evaluation only,
+        through linearize(..., variance=False)."""
+        self._no_full_q('transition_jacobians')
+        Do, Da = self.out_dim, self.in_dim - self.out_dim
+        if Da < 0:
+            raise ValueError('transition_jacobians: the GP input dimension %d is smaller than its output dimension %d'
+                             % (self.in_dim, self.out_dim))
+        dev = self.zeta_pos.device
+        h = _f64(h, dev)
+        assert h.dim() == 2 and h.shape[1] == Do, 'h (N, out_dim)'
+        if Da == 0:
+            assert a is None or tuple(a.shape) == (h.shape[0], 0), 'a: None or (N, 0) when the GP takes the state alone'
+            X = h
+        else:
+            a = _f64(a, dev)
+            assert tuple(a.shape) == (h.shape[0], Da), 'a (N, in_dim - out_dim)'
+            X = torch.cat([h, a], dim=1)
+        dmean = self.linearize(X, variance=False)[2]
+        A = dmean[:, :, :Do] + torch.eye(Do, dtype=torch.float64, device=dev)
+        return A, dmean[:, :, Do:].contiguous()

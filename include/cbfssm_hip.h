@@ -241,6 +241,30 @@ int cbfssm_gp_tail_fullq_f64(const cbfssm_pack_layout* layout, const double* pac
                              double* work, double* gflat, void* stream);
 
 /*
+ * ---- local linear model of ONE sparse GP: the Jacobians of GPModel.predict (gp_tf.py:132-161) with respect to its inputs,
+ * what the reference gets from tf.gradients(fmean[:, d], Xnew) and tf.gradients(fvar[:, d], Xnew), once per output
+ * dimension d, through gp_tf.py:132-161 -- for EKF-style filtering, iLQR / MPC around a learned transition, sensitivities.
+ *
+ *   dmean[n][d][i] = d fmean[n][d] / d X[n][i],   dvar[n][d][i] = d fvar[n][d] / d X[n][i]      (the unscaled inputs)
+ *
+ * cbfssm_gp_linearize_f64: pack prepared (diagonal q(z)); X (npts, D) -> dmean (npts, Do, D), and when the pointers are not
+ *   NULL fmean, fvar (npts, Do) and dvar (npts, Do, D).  dvar NULL: the mean part alone, without the K^-1 product per output
+ *   dimension that the variance needs; dmean and fmean are then bitwise those of the full call.  One pre-kernel forms
+ *   alpha = K^-1 mu in `work` (cbfssm_gp_linearize_work_elems doubles; dense form: Kinv mu, two-triangular form:
+ *   L^-T (L^-1 mu)), then ONE launch does all output dimensions: per 16 points the kernel tile, A2 = K^-1 k and fvar in the
+ *   form layout->gp_form asks for, and per dimension alpha_d o k, 2 (K^-1 (A2 o zeta_var_d) - A2) o k (dense K^-1 image in
+ *   both forms) and their products with the pack's (Z / lengthscale)^T image on the f64 MFMA units.  Persistent workgroups,
+ *   at most as many as cbfssm_gp_predict_bwd_workgroups names.
+ * No atomics, no allocation, no host synchronisation, every output entry has one writer, two calls are bitwise identical,
+ * and the results of a point do not depend on the other points of the call; nothing is launched at npts = 0.  Limits as
+ * cbfssm_gp_predict_f64 (M <= 320, D <= 24, Do <= 16), else -3 before any launch; NULL layout, pack, X, dmean or work, or
+ * npts < 0: -1.  The count is host arithmetic in 64 bits and returns -1 for a bad layout.
+ */
+int64_t cbfssm_gp_linearize_work_elems(const cbfssm_pack_layout* layout);
+int cbfssm_gp_linearize_f64(const cbfssm_pack_layout* layout, const double* pack, const double* X, int64_t npts,
+                            double* fmean, double* fvar, double* dmean, double* dvar, double* work, void* stream);
+
+/*
  * ---- differentiable GP rollout: the time loop of ONE sparse GP with per-chain inputs, and its adjoint.
  * Replaces the loop bodies of Voliro's recognition run (cbfssm/model/voliro.py:139-186: one run from h = 0, backwards in
  * time, GP input (h, u_t, y_t) with a per-particle u_t) and of the free-running transition of a trained CBF-SSM
