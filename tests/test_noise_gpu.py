@@ -35,7 +35,10 @@ def test_generator_words_and_known_answer():
 
 
 @pytest.mark.parametrize('seed,offset,n', [(1, 0, 1), (1, 1, 1), (7, 0, 1000), (7, 3, 1001), (2 ** 63 + 11, 2 ** 33 + 1, 4097),
-                                            (5, 0, 3_000_000)])
+                                            (5, 0, 3_000_000),
+                                            # past one sweep of the launch's 16384 x 256 pairs, from an odd offset: the
+                                            # grid-stride loop's second iteration (the C5 draw takes it)
+                                            (7, 1, 2 * 16384 * 256 + 3)])
 def test_normal_matches_restatement(seed, offset, n):
     from oracle import philox as ph
     got, want = _normal(seed, offset, n), ph.normal(seed, offset, n)
