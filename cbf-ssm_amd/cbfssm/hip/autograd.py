@@ -3,7 +3,9 @@ functions of one sparse GP (`gp_predict`, `gp_prior_kl`, further down; `gp_predi
 full-covariance q(z), `gp_conditional_diag` behind `gp_tf.conditional`), its recurrence over time (`gp_rollout`), the same
 recurrence with a masked Gaussian filter update per step (`gp_filter`) and the rigid-body filter loop of the Voliro model
 (`rigid_filter`, at the end).  `gp_linearize_eval` is evaluation only: the Jacobians of the GP mean and variance with respect
-to the inputs, all output dimensions in one launch.
+to the inputs, all output dimensions in one launch; `gp_ekf_eval`, evaluation only as well, runs the extended Kalman filter
+those Jacobians are for -- a mean and a full state covariance per chain through time, conditioned where there are
+observations -- as one launch.
 
 The CBF-SSM loss:
 
@@ -651,6 +653,71 @@ def gp_linearize_eval(pack, X, variance=True):
         _l.check(lib.cbfssm_gp_linearize_f64(C.byref(lay), _ptr(pack.buf), _ptr(X), n, _ptr(fmean), _ptr(fvar), _ptr(dmean),
                                              _ptr(dvar), _ptr(work), _stream()), 'cbfssm_gp_linearize_f64')
     return fmean, fvar, dmean, dvar
+
+
+# ---- the extended Kalman filter over the transition of one sparse GP: a Gaussian belief per chain through time -------------
+#
+#     means, covs, loglik = gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=None)
+#
+#     for t in 0..T-1:
+#         x = concat(m, a[t]);  f, fv = predict(x);  A = I + d fmean / d x [:, :Do]        (gp_tf.py:132-161 and its Jacobian)
+#         m = m + f;  P = A P A^T + diag(fv + var_x)                                      (cbfssm.py:199-206)
+#         where cond[t, n], for j in 0..Dy-1:  s = P[j, j] + var_y[j];  delta = y[t, n, j] - m[j];  g = P[:, j] / s
+#                                              m += g delta;  P -= s g g^T;  loglik[n] -= (log(2 pi s) + delta^2 / s) / 2
+#         means[t] = m;  covs[t] = P
+#
+# the scalar updates being the joint Kalman update with H = [I_Dy 0], R = diag(var_y) (cbfssm.py:245-251: the first dim_y
+# state dimensions are observed).  One launch for all steps (cbfssm_gp_ekf_f64) instead of a loop over predict +
+# transition_jacobians + batched tensor-library algebra with one prepare per step.
+
+def gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=None):
+    """(means (T, N, Do), covs (T, N, Do, Do), loglik (N)) on a pack that is already prepared.  m0 (N, Do), P0 (N, Do, Do)
+    or None (zero; only its lower triangle is read), a (T, N, D - Do) or None when the GP takes the state alone, y
+    (T, N, Dy) with 1 <= Dy <= Do, var_x (Do) constrained values or None, var_y (Dy) constrained values, cond (T, N) of
+    0 / 1 (any dtype; None: condition everywhere).  A y entry where cond = 0 is never used and may be NaN.  Evaluation
+    only: no grad_fn, no host synchronisation, nothing is launched without a chain or a step (loglik is then zero)."""
+    lib = _l.load()
+    lay, dev = pack.layout, pack.buf.device
+    Do, Da = pack.Do, pack.D - pack.Do
+    if Da < 0:
+        raise ValueError('gp_ekf: the GP input dimension %d is smaller than its output dimension %d' % (pack.D, pack.Do))
+    f64 = lambda t: torch.as_tensor(t, dtype=torch.float64, device=dev).detach().contiguous()
+    with torch.no_grad():
+        y, m0, var_y = f64(y), f64(m0), f64(var_y)
+        assert y.dim() == 3 and m0.dim() == 2 and m0.shape == (y.shape[1], Do), 'y (T, N, Dy), m0 (N, Do)'
+        T, N, Dy = y.shape
+        if not 1 <= Dy <= Do:
+            raise ValueError('gp_ekf: y observes the first Dy state dimensions, 1 <= Dy <= %d (got %d)' % (Do, Dy))
+        assert tuple(var_y.shape) == (Dy,), 'var_y (Dy)'
+        if P0 is not None:
+            P0 = f64(P0)
+            assert tuple(P0.shape) == (N, Do, Do), 'P0 (N, Do, Do)'
+        if Da == 0:
+            assert a is None or tuple(a.shape) == (T, N, 0), 'a: None or (T, N, 0) when the GP takes the state alone'
+            a = None
+        else:
+            a = f64(a)
+            assert tuple(a.shape) == (T, N, Da), 'a (T, N, D - Do)'
+        if var_x is not None:
+            var_x = f64(var_x)
+            assert tuple(var_x.shape) == (Do,), 'var_x (Do)'
+        if cond is not None:
+            cond = torch.as_tensor(cond, device=dev)
+            assert tuple(cond.shape) == (T, N), 'cond (T, N)'
+            cond = (cond != 0).to(torch.float64).contiguous()
+        means = torch.empty(T, N, Do, dtype=torch.float64, device=dev)
+        covs = torch.empty(T, N, Do, Do, dtype=torch.float64, device=dev)
+        if N == 0 or T == 0:
+            return means, covs, torch.zeros(N, dtype=torch.float64, device=dev)
+        loglik = torch.empty(N, dtype=torch.float64, device=dev)
+        nwork = int(lib.cbfssm_gp_ekf_work_elems(C.byref(lay)))
+        if nwork < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_ekf_work_elems refused the layout')
+        work = torch.empty(nwork, dtype=torch.float64, device=dev)
+        _l.check(lib.cbfssm_gp_ekf_f64(C.byref(lay), _ptr(pack.buf), _ptr(m0), _ptr(P0), _ptr(a), _ptr(y), _ptr(cond),
+                                       _ptr(var_x), _ptr(var_y), Dy, N, T, _ptr(means), _ptr(covs), _ptr(loglik), _ptr(work),
+                                       _stream()), 'cbfssm_gp_ekf_f64')
+    return means, covs, loglik
 
 
 # ---- the filter loop of one sparse GP: the rollout with a Gaussian filter update per step and chain behind a mask --------

@@ -30,6 +30,12 @@ respect to Xnew for all output dimensions in one launch -- what the reference ge
 output dimension through gp_tf.py:132-161 -- and `GPModel.transition_jacobians(h, a)` the matrices A = d m / d h,
 B = d m / d a of the recurrence m = h + fmean(concat(h, a)) that `rollout` and `filter` run (EKF-style filtering, iLQR / MPC
 around a learned transition).  Both are evaluation only and for the diagonal q(z).
+
+`GPModel.ekf(m0, P0, a, y, var_x, var_y, cond=None)` runs the recursion those Jacobians are for: the extended Kalman filter
+over the GP as a transition -- per chain a mean and a full state covariance propagated through m = h + fmean, conditioned
+on observations of the first Dy state dimensions where `cond` says so (cbfssm/model/cbfssm.py:199-221,245-251) -- with the
+log-likelihood of each chain, as one fused launch.  cond = 0 everywhere is a deterministic multi-step forecast with its
+covariances.  Evaluation only, diagonal q(z).
 """
 import ctypes as C
 import numpy as np
@@ -196,8 +202,8 @@ class GPModel:
     q_full=True: a full-covariance q(z_d) = N(zeta_mean[:, d], L_d L_d^T) per output dimension (the zeta_std.ndims == 3
     branch of gp_tf.py:150-159).  The third leaf is then `zeta_sqrt` (Do, M, M), unconstrained, initialised to
     sqrt(zeta_var) I; only its lower triangle is read and its gradient above the diagonal is exactly zero.  `zeta_std`
-    returns the factors L_d, `zeta_var` the marginal variances diag(L_d L_d^T) as (M, Do).  `rollout` and `filter` raise
-    ValueError on such a model."""
+    returns the factors L_d, `zeta_var` the marginal variances diag(L_d L_d^T) as (M, Do).  `rollout`, `filter`,
+    `linearize`, `transition_jacobians` and `ekf` raise ValueError on such a model."""
 
     def __init__(self, in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var, dtype='float64',
                  device=None, seed=None, q_full=False):
@@ -342,6 +348,34 @@ class GPModel:
         Xnew = _f64(Xnew, self.zeta_pos.device)
         pack = self._prepared() if Xnew.shape[0] else self._pack                 # (nothing runs without a point)
         return _ag.gp_linearize_eval(pack, Xnew, variance=variance)
+
+    def ekf(self, m0, P0, a, y, var_x, var_y, cond=None):
+        """An addition to the reference's surface: the extended Kalman filter over this GP as the transition of CBF-SSM
+        (cbfssm/model/cbfssm.py:199-221) with its observation model (cbfssm.py:245-251: the first Dy state dimensions plus
+        N(0, diag(var_y))) -- a Gaussian belief per chain, mean and full covariance, as one launch:
+
+            for t in 0..T-1:
+                x = concat(m, a[t]);  f, fv = predict(x);  A = I + d fmean / d x [:, :out_dim]     (linearize's dmean)
+                m = m + f;  P = A P A^T + diag(fv + var_x)
+                where cond[t, n], for j in 0..Dy-1:  s = P[j, j] + var_y[j];  delta = y[t, n, j] - m[j];  g = P[:, j] / s
+                                                     m += g delta;  P -= s g g^T
+                                                     loglik[n] -= (log(2 pi s) + delta^2 / s) / 2
+                means[t] = m;  covs[t] = P
+
+        which is the joint Kalman update with H = [I_Dy 0], R = diag(var_y), and loglik[n] the log-likelihood of the
+        conditioned observations of chain n, free of Monte-Carlo noise.  m0 (N, out_dim), P0 (N, out_dim, out_dim) or None
+        (zero; only the lower triangle is read), a (T, N, in_dim - out_dim) or None, y (T, N, Dy) with 1 <= Dy <= out_dim,
+        var_x (out_dim) constrained values or None, var_y (Dy) constrained values, cond (T, N) of 0 / 1 or None (condition
+        everywhere): zeros mark missing observations -- y may hold NaN there, it is never read into a result -- and
+        cond = 0 everywhere is uncertainty propagation, a multi-step forecast with its covariances, loglik exactly 0.
+        Returns (means (T, N, out_dim), covs (T, N, out_dim, out_dim), loglik (N)); every covs[t, n] is bitwise symmetric.
+        Evaluation only: the results carry no grad_fn whatever the leaves or the inputs ask for.  Raises ValueError on a
+        q_full=True model."""
+        self._no_full_q('ekf')
+        from ..hip import autograd as _ag
+        y = _f64(y, self.zeta_pos.device)
+        pack = self._prepared() if y.shape[0] * y.shape[1] else self._pack       # (nothing runs without a chain or a step)
+        return _ag.gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond)
 
     def transition_jacobians(self, h, a=None):
         """The local linear model of the recurrence `rollout` and `filter` run, m = h + fmean(concat(h, a)):

@@ -1,0 +1,2 @@
+#include "cbfssm_gp_ekf.hpp"
+CBF_GPEKF_INSTANTIATE(4)

@@ -265,6 +265,43 @@ int cbfssm_gp_linearize_f64(const cbfssm_pack_layout* layout, const double* pack
                             double* fmean, double* fvar, double* dmean, double* dvar, double* work, void* stream);
 
 /*
+ * ---- extended Kalman filter over the transition of ONE sparse GP: a Gaussian belief (m, P) per chain, carried through
+ * time by the local linear model above inside the recurrence of CBF-SSM (cbfssm/model/cbfssm.py:199-221) and conditioned
+ * on observations of the first Dy state dimensions (cbfssm.py:245-251), y = x[:Dy] + N(0, diag(var_y)).  Forward in time,
+ * evaluation only, diagonal q(z).
+ *
+ *   for t = 0 .. T-1:
+ *       x = concat(m, a[t]);  f, fv = GPModel.predict(x);  J = d fmean / d x [:, :Do]            gp_tf.py:132-161
+ *       A = I + J;  m- = m + f;  P- = A P A^T + diag(fv + var_x)                                 cbfssm.py:199-206
+ *       cond[t, n] != 0, for j = 0 .. Dy-1 in this order:                                        cbfssm.py:212-221,245-251
+ *           s = P-[j][j] + var_y[j];  delta = y[t][n][j] - m-[j]
+ *           m- += P-[:, j] delta / s;  P-[i][k] -= (P-[i][j] P-[k][j]) / s;  loglik[n] -= (log(2 pi s) + delta^2 / s) / 2
+ *       m, P = m-, P-;  means[t][n] = m;  covs[t][n] = P
+ *
+ * The scalar updates in this order are the joint Kalman update with H = [I_Dy 0], R = diag(var_y), and loglik[n] is
+ * sum_t log N(y[t][n]; H m-, H P- H^T + R) over the conditioned steps.
+ *
+ * cbfssm_gp_ekf_f64 (gp_tf.py:132-161, cbfssm.py:199-221,245-251): pack prepared (diagonal q(z)); m0 (N, Do), P0
+ * (N, Do, Do) of which only the lower triangle is read, or NULL = 0, a (T, N, D - Do) or NULL when D == Do, y (T, N, Dy),
+ * cond (T, N) doubles 0 / 1 or NULL = condition everywhere, var_x (Do) constrained values or NULL, var_y (Dy) constrained
+ * values -> means (T, N, Do), covs (T, N, Do, Do), loglik (N): every entry written once, covs[t][n] bitwise symmetric.
+ * The branch is a select: a y entry at cond = 0 may be NaN and reaches no output; cond = 0 everywhere propagates the
+ * belief without data (loglik exactly 0).  One pre-kernel forms alpha = K^-1 mu in `work` (cbfssm_gp_ekf_work_elems
+ * doubles, as cbfssm_gp_linearize_f64 does), then ONE launch runs all steps, one workgroup per 16 chains, both GP forms
+ * (layout->gp_form; A of the two-triangular form through LDS and workgroup barriers, no flag hand-off).
+ * No atomics, no allocation, no host synchronisation, two calls are bitwise identical, and the results of a chain do not
+ * depend on the other chains of the call; nothing is launched (and nothing written) at N = 0 or T = 0.  Limits as
+ * cbfssm_gp_predict_f64 (M <= 320, D <= 24, Do <= 16) plus Do <= D, 1 <= Dy <= Do, N <= 2^30, T <= 2^24, else -3 before any
+ * launch; NULL layout, pack, m0, y, var_y, means, covs, loglik or work, NULL a with D > Do, or N, T, Dy < 0: -1.  The
+ * count is host arithmetic in 64 bits and returns -1 for a bad layout.
+ */
+int64_t cbfssm_gp_ekf_work_elems(const cbfssm_pack_layout* layout);      /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
+int cbfssm_gp_ekf_f64(const cbfssm_pack_layout* layout, const double* pack, const double* m0, const double* P0,
+                      const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                      int Dy, int64_t N, int64_t T, double* means, double* covs, double* loglik, double* work,
+                      void* stream);                                     /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
+
+/*
  * ---- differentiable GP rollout: the time loop of ONE sparse GP with per-chain inputs, and its adjoint.
  * Replaces the loop bodies of Voliro's recognition run (cbfssm/model/voliro.py:139-186: one run from h = 0, backwards in
  * time, GP input (h, u_t, y_t) with a per-particle u_t) and of the free-running transition of a trained CBF-SSM
