@@ -5,7 +5,8 @@ recurrence with a masked Gaussian filter update per step (`gp_filter`) and the r
 (`rigid_filter`, at the end).  `gp_linearize_eval` is evaluation only: the Jacobians of the GP mean and variance with respect
 to the inputs, all output dimensions in one launch; `gp_ekf_eval`, evaluation only as well, runs the extended Kalman filter
 those Jacobians are for -- a mean and a full state covariance per chain through time, conditioned where there are
-observations -- as one launch.
+observations -- as one launch; `gp_eks_eval` adds the Rauch-Tung-Striebel sweep behind it: smoothed and one-step predictive
+moments, the smoothed initial belief and the lag-one cross-covariances.
 
 The CBF-SSM loss:
 
@@ -25,6 +26,7 @@ process group) are computed only when u or y requires grad, or when `input_grads
 `input_grads=False` the call is the engine's default adjoint and u, y receive no gradient.  Nothing here computes on
 the host or in the tensor library: a missing kernel is the engine's error.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -718,6 +720,79 @@ def gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=None):
                                        _ptr(var_x), _ptr(var_y), Dy, N, T, _ptr(means), _ptr(covs), _ptr(loglik), _ptr(work),
                                        _stream()), 'cbfssm_gp_ekf_f64')
     return means, covs, loglik
+
+
+# ---- the Rauch-Tung-Striebel smoother behind that filter: every state given ALL observations of its chain ----------------
+#
+#     res = gp_eks_eval(pack, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False)          (an EksResult)
+#
+#     forward: gp_ekf_eval as it is, which also leaves m-_t, P-_t (before conditioning) and A_t P_{t-1} of every step
+#     (ms, Ps)[T-1] = (means, covs)[T-1]
+#     for t in T-1..0:
+#         G = (A_t P_{t-1})^T (P-_t)^-1                       (Cholesky factorisation of P-_t, two triangular solves)
+#         ms[t-1] = m[t-1] + G (ms[t] - m-_t);  Ps[t-1] = P[t-1] + G (Ps[t] - P-_t) G^T;  lag_one[t] = G Ps[t]
+#
+# with (m, P)[-1] = (m0, P0): the last iteration gives the smoothed initial belief.  Four launches on one stream
+# (cbfssm_gp_eks_f64) instead of ekf + one transition_jacobians per step + a loop of batched tensor-library solves.
+
+EksResult = collections.namedtuple('EksResult', 'smeans scovs loglik means covs pmeans pcovs init_mean init_cov lag_one info')
+
+
+def gp_eks_eval(pack, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):
+    """EksResult(smeans (T, N, Do), scovs (T, N, Do, Do), loglik (N), means, covs (the filtered moments and loglik bitwise
+    those of gp_ekf_eval), pmeans (T, N, Do), pcovs (T, N, Do, Do) (the one-step predictive moments, before conditioning),
+    init_mean (N, Do), init_cov (N, Do, Do) (the smoothed belief before step 0), lag_one (T, N, Do, Do) with
+    lag_one[t] = Cov(x_{t-1}, x_t | y) or None unless asked for, info (N) int64) on a pack that is already prepared;
+    arguments as gp_ekf_eval.  info[n] = 0, or t + 1 where the factorisation of P-_t met a pivot <= 0 or not finite (P0 not
+    positive semi-definite): that chain's smoothed results at times < t, its initial belief and lag_one[<= t] are NaN,
+    everything else is unaffected.  Every scovs[t, n] and init_cov[n] is bitwise symmetric.  Evaluation only: no grad_fn,
+    no host synchronisation, nothing is launched without a chain or a step (loglik is then zero)."""
+    lib = _l.load()
+    lay, dev = pack.layout, pack.buf.device
+    Do, Da = pack.Do, pack.D - pack.Do
+    if Da < 0:
+        raise ValueError('gp_eks: the GP input dimension %d is smaller than its output dimension %d' % (pack.D, pack.Do))
+    f64 = lambda t: torch.as_tensor(t, dtype=torch.float64, device=dev).detach().contiguous()
+    with torch.no_grad():
+        y, m0, var_y = f64(y), f64(m0), f64(var_y)
+        assert y.dim() == 3 and m0.dim() == 2 and m0.shape == (y.shape[1], Do), 'y (T, N, Dy), m0 (N, Do)'
+        T, N, Dy = y.shape
+        if not 1 <= Dy <= Do:
+            raise ValueError('gp_eks: y observes the first Dy state dimensions, 1 <= Dy <= %d (got %d)' % (Do, Dy))
+        assert tuple(var_y.shape) == (Dy,), 'var_y (Dy)'
+        if P0 is not None:
+            P0 = f64(P0)
+            assert tuple(P0.shape) == (N, Do, Do), 'P0 (N, Do, Do)'
+        if Da == 0:
+            assert a is None or tuple(a.shape) == (T, N, 0), 'a: None or (T, N, 0) when the GP takes the state alone'
+            a = None
+        else:
+            a = f64(a)
+            assert tuple(a.shape) == (T, N, Da), 'a (T, N, D - Do)'
+        if var_x is not None:
+            var_x = f64(var_x)
+            assert tuple(var_x.shape) == (Do,), 'var_x (Do)'
+        if cond is not None:
+            cond = torch.as_tensor(cond, device=dev)
+            assert tuple(cond.shape) == (T, N), 'cond (T, N)'
+            cond = (cond != 0).to(torch.float64).contiguous()
+        new = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)
+        means, covs, pmeans, pcovs, cross = new(T, N, Do), new(T, N, Do, Do), new(T, N, Do), new(T, N, Do, Do), new(T, N, Do, Do)
+        smeans, scovs, sm_init, sP_init = new(T, N, Do), new(T, N, Do, Do), new(N, Do), new(N, Do, Do)
+        lag1 = new(T, N, Do, Do) if lag_one else None
+        if N == 0 or T == 0:
+            return EksResult(smeans, scovs, torch.zeros(N, dtype=torch.float64, device=dev), means, covs, pmeans, pcovs, sm_init,
+                             sP_init, lag1, torch.zeros(N, dtype=torch.int64, device=dev))
+        loglik, info = new(N), new(N)
+        nwork = int(lib.cbfssm_gp_eks_work_elems(C.byref(lay)))
+        if nwork < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_eks_work_elems refused the layout')
+        work = new(nwork)
+        _l.check(lib.cbfssm_gp_eks_f64(C.byref(lay), _ptr(pack.buf), _ptr(m0), _ptr(P0), _ptr(a), _ptr(y), _ptr(cond),
+                                       _ptr(var_x), _ptr(var_y), Dy, N, T, _ptr(means), _ptr(covs), _ptr(loglik), _ptr(pmeans),
+                                       _ptr(pcovs), _ptr(cross), _ptr(smeans), _ptr(scovs), _ptr(sm_init), _ptr(sP_init),
+                                       _ptr(lag1), _ptr(info), _ptr(work), _stream()), 'cbfssm_gp_eks_f64')
+    return EksResult(smeans, scovs, loglik, means, covs, pmeans, pcovs, sm_init, sP_init, lag1, info.to(torch.int64))
 
 
 # ---- the filter loop of one sparse GP: the rollout with a Gaussian filter update per step and chain behind a mask --------

@@ -42,6 +42,7 @@ SYMBOLS = (
     'cbfssm_gp_fullq_wd_f64', 'cbfssm_gp_fullq_lbar_f64', 'cbfssm_gp_tail_fullq_f64', 'cbfssm_gp_fullq_predict_f64',
     'cbfssm_gp_linearize_work_elems', 'cbfssm_gp_linearize_f64',
     'cbfssm_gp_ekf_work_elems', 'cbfssm_gp_ekf_f64',
+    'cbfssm_gp_eks_work_elems', 'cbfssm_gp_eks_f64',
 )
 
 
@@ -201,6 +202,9 @@ def load():
     lib.cbfssm_gp_ekf_work_elems.restype = i64
     lib.cbfssm_gp_ekf_work_elems.argtypes = [C.POINTER(PackLayout)]
     lib.cbfssm_gp_ekf_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 5
+    lib.cbfssm_gp_eks_work_elems.restype = i64
+    lib.cbfssm_gp_eks_work_elems.argtypes = [C.POINTER(PackLayout)]
+    lib.cbfssm_gp_eks_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 14
     for name in ('cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_bwd_workgroups'):
         getattr(lib, name).restype = i64
         getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]

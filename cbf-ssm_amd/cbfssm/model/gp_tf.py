@@ -36,6 +36,8 @@ over the GP as a transition -- per chain a mean and a full state covariance prop
 on observations of the first Dy state dimensions where `cond` says so (cbfssm/model/cbfssm.py:199-221,245-251) -- with the
 log-likelihood of each chain, as one fused launch.  cond = 0 everywhere is a deterministic multi-step forecast with its
 covariances.  Evaluation only, diagonal q(z).
+`GPModel.eks(..., lag_one=False)` is that filter followed by the Rauch-Tung-Striebel sweep: smoothed and one-step predictive
+moments, the smoothed initial belief and, on request, the lag-one cross-covariances (the E-step of EM), in four launches.
 """
 import ctypes as C
 import numpy as np
@@ -203,7 +205,7 @@ class GPModel:
     branch of gp_tf.py:150-159).  The third leaf is then `zeta_sqrt` (Do, M, M), unconstrained, initialised to
     sqrt(zeta_var) I; only its lower triangle is read and its gradient above the diagonal is exactly zero.  `zeta_std`
     returns the factors L_d, `zeta_var` the marginal variances diag(L_d L_d^T) as (M, Do).  `rollout`, `filter`,
-    `linearize`, `transition_jacobians` and `ekf` raise ValueError on such a model."""
+    `linearize`, `transition_jacobians`, `ekf` and `eks` raise ValueError on such a model."""
 
     def __init__(self, in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var, dtype='float64',
                  device=None, seed=None, q_full=False):
@@ -376,6 +378,33 @@ class GPModel:
         y = _f64(y, self.zeta_pos.device)
         pack = self._prepared() if y.shape[0] * y.shape[1] else self._pack       # (nothing runs without a chain or a step)
         return _ag.gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond)
+
+    def eks(self, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):
+        """The Rauch-Tung-Striebel smoother behind `ekf`: the belief about every state given ALL observations of its chain.
+        The forward pass is `ekf` itself (arguments, checks and the results means, covs, loglik are its own, bitwise); it
+        also hands out the one-step predictive moments, and a backward sweep follows:
+
+            pmeans[t] = m-_t;  pcovs[t] = P-_t = A_t P_{t-1} A_t^T + diag(fv + var_x)        (before conditioning)
+            (smeans, scovs)[T-1] = (means, covs)[T-1]
+            for t in T-1..0:   G = (A_t P_{t-1})^T (P-_t)^-1
+                               smeans[t-1] = means[t-1] + G (smeans[t] - pmeans[t])
+                               scovs[t-1]  = covs[t-1] + G (scovs[t] - pcovs[t]) G^T
+                               lag_one[t]  = G scovs[t] = Cov(x_{t-1}, x_t | y)
+
+        where time -1 is the initial belief (m0, P0): the last iteration gives (init_mean, init_cov).  Returns the
+        namedtuple EksResult(smeans (T, N, out_dim), scovs (T, N, out_dim, out_dim), loglik (N), means, covs, pmeans,
+        pcovs, init_mean (N, out_dim), init_cov (N, out_dim, out_dim), lag_one (T, N, out_dim, out_dim) or None unless
+        lag_one=True, info (N) int64) -- what offline state estimation and the E-step of EM over the transition and noise
+        parameters need.  scovs and init_cov are bitwise symmetric.  info[n] is 0, or t + 1 where P-_t of chain n was not
+        positive definite (possible only when P0 is not positive semi-definite): that chain's smoothed results before t,
+        its initial belief and lag_one[<= t] are then NaN and nothing else is affected.  Four launches, no host
+        synchronisation.  Evaluation only: the results carry no grad_fn whatever the leaves or the inputs ask for.  Raises
+        ValueError on a q_full=True model and when in_dim < out_dim."""
+        self._no_full_q('eks')
+        from ..hip import autograd as _ag
+        y = _f64(y, self.zeta_pos.device)
+        pack = self._prepared() if y.shape[0] * y.shape[1] else self._pack       # (nothing runs without a chain or a step)
+        return _ag.gp_eks_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond, lag_one=lag_one)
 
     def transition_jacobians(self, h, a=None):
         """The local linear model of the recurrence `rollout` and `filter` run, m = h + fmean(concat(h, a)):

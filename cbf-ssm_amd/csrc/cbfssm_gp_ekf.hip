@@ -36,7 +36,7 @@ static bool gp_ekf_nblk_ok(int NBLK)
 }
 
 // the limits of cbfssm_gp_predict_f64, checked on the layout itself (as cbfssm_gp_linearize_f64 does), and D >= Do
-static bool gp_ekf_layout_ok(const cbfssm_pack_layout* L)
+bool gp_ekf_layout_ok(const cbfssm_pack_layout* L)
 {
     if (!L) return false;
     if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
@@ -46,6 +46,44 @@ static bool gp_ekf_layout_ok(const cbfssm_pack_layout* L)
     if (L->KS != 4 * L->NBLK) return false;
     if (L->JB != (4 * L->DK + 1 + 15) / 16) return false;
     return true;
+}
+
+// what cbfssm_gp_ekf_f64 and cbfssm_gp_eks_f64 (cbfssm_gp_eks.hip) refuse before they look at a pointer
+int gp_ekf_check_sizes(const char* who, const cbfssm_pack_layout* L, int Dy, int64_t N, int64_t T)
+{
+    if (!L) return fail(-1, "null layout");
+    if (N < 0 || T < 0 || Dy < 0) return fail(-1, "negative size");
+    if (!gp_ekf_layout_ok(L))
+        return fail(-3, "%s limits: M <= %d, Do <= D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
+                    who, CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
+    if (Dy < 1 || Dy > L->Do) return fail(-3, "%s: 1 <= Dy <= Do (Dy=%d Do=%d)", who, Dy, L->Do);
+    if (N > (int64_t(1) << 30) || T > (int64_t(1) << 24)) return fail(-3, "%s: N <= 2^30, T <= 2^24", who);
+    return 0;
+}
+
+// the alpha pre-kernel and the filter launch; pmeans, pcovs, cross: all three or none (the smoother's inputs)
+int gp_ekf_launch(const char* who, const cbfssm_pack_layout* L, const double* pack, const double* m0, const double* P0,
+                  const double* a, const double* y, const double* cond, const double* var_x, const double* var_y, int Dy,
+                  int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans, double* pcovs,
+                  double* cross, double* work, hipStream_t st)
+{
+    const int tri = (L->gp_form == CBFSSM_GP_FORM_TRI);
+    hipLaunchKernelGGL(gp_lin_alpha_kernel, dim3(16), dim3(256), 0, st, pack + L->Kinv, pack + L->Linvt, pack + L->muB, L->M,
+                       L->Do, 16 * L->NBLK, tri, work);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(-int(e) - 1000, "%s: alpha launch failed", who);
+    GpEkfArgs k;
+    memset(&k, 0, sizeof(k));
+    k.pk.Bp = pack + L->Bp; k.pk.Zp = pack + L->Zp; k.pk.cz = pack + L->cz; k.pk.muA = pack + L->muA;
+    k.pk.invl = pack + L->invl; k.pk.scal = pack + L->scal; k.pk.KSr = (L->M + 3) / 4;
+    k.pk.Wp = pack + L->Wp; k.pk.WTp = pack + L->WTp;
+    k.rk.muB = pack + L->muB; k.rk.s2B = pack + L->s2B; k.rk.ZT = pack + L->ZT;
+    k.m0 = m0; k.P0 = P0; k.a = a; k.y = y; k.cond = cond; k.var_x = var_x; k.var_y = var_y; k.alpha = work;
+    k.means = means; k.covs = covs; k.loglik = loglik; k.pmeans = pmeans; k.pcovs = pcovs; k.cross = cross;
+    k.N = int(N); k.T = int(T); k.M = L->M; k.D = L->D; k.Do = L->Do; k.Dy = Dy; k.tri = tri;
+    int rc = dispatch_gp_ekf(L->NBLK, L->DK, k, st);
+    if (rc) return fail(rc, "%s launch failed (NBLK=%d DK=%d rc=%d)", who, L->NBLK, L->DK, rc);
+    return 0;
 }
 
 }  // namespace cbfssm
@@ -64,34 +102,12 @@ int cbfssm_gp_ekf_f64(const cbfssm_pack_layout* L, const double* pack, const dou
                       const double* y, const double* cond, const double* var_x, const double* var_y, int Dy, int64_t N,
                       int64_t T, double* means, double* covs, double* loglik, double* work, void* stream)
 {
-    if (!L) return fail(-1, "null layout");
-    if (N < 0 || T < 0 || Dy < 0) return fail(-1, "negative size");
-    if (!gp_ekf_layout_ok(L))
-        return fail(-3, "gp_ekf limits: M <= %d, Do <= D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
-                    CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
-    if (Dy < 1 || Dy > L->Do) return fail(-3, "gp_ekf: 1 <= Dy <= Do (Dy=%d Do=%d)", Dy, L->Do);
-    if (N > (int64_t(1) << 30) || T > (int64_t(1) << 24)) return fail(-3, "gp_ekf: N <= 2^30, T <= 2^24");
+    if (int rc = gp_ekf_check_sizes("gp_ekf", L, Dy, N, T)) return rc;
     if (!pack || !m0 || !y || !var_y || !means || !covs || !loglik || !work) return fail(-1, "null pointer");
     if (L->D > L->Do && !a) return fail(-1, "null a with D > Do");
     if (N == 0 || T == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const int tri = (L->gp_form == CBFSSM_GP_FORM_TRI);
-    hipLaunchKernelGGL(gp_lin_alpha_kernel, dim3(16), dim3(256), 0, st, pack + L->Kinv, pack + L->Linvt, pack + L->muB, L->M,
-                       L->Do, 16 * L->NBLK, tri, work);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-int(e) - 1000, "gp_ekf: alpha launch failed");
-    GpEkfArgs k;
-    memset(&k, 0, sizeof(k));
-    k.pk.Bp = pack + L->Bp; k.pk.Zp = pack + L->Zp; k.pk.cz = pack + L->cz; k.pk.muA = pack + L->muA;
-    k.pk.invl = pack + L->invl; k.pk.scal = pack + L->scal; k.pk.KSr = (L->M + 3) / 4;
-    k.pk.Wp = pack + L->Wp; k.pk.WTp = pack + L->WTp;
-    k.rk.muB = pack + L->muB; k.rk.s2B = pack + L->s2B; k.rk.ZT = pack + L->ZT;
-    k.m0 = m0; k.P0 = P0; k.a = a; k.y = y; k.cond = cond; k.var_x = var_x; k.var_y = var_y; k.alpha = work;
-    k.means = means; k.covs = covs; k.loglik = loglik;
-    k.N = int(N); k.T = int(T); k.M = L->M; k.D = L->D; k.Do = L->Do; k.Dy = Dy; k.tri = tri;
-    int rc = dispatch_gp_ekf(L->NBLK, L->DK, k, st);
-    if (rc) return fail(rc, "gp_ekf launch failed (NBLK=%d DK=%d rc=%d)", L->NBLK, L->DK, rc);
-    return 0;
+    return gp_ekf_launch("gp_ekf", L, pack, m0, P0, a, y, cond, var_x, var_y, Dy, N, T, means, covs, loglik, nullptr, nullptr,
+                         nullptr, work, (hipStream_t)stream);
 }
 
 }  // extern "C"

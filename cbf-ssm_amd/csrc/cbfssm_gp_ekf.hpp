@@ -55,6 +55,9 @@ struct GpEkfArgs {
     double* means;         // (T, N, Do)
     double* covs;          // (T, N, Do, Do)
     double* loglik;        // (N)
+    double* pmeans;        // (T, N, Do)      m- of every step, before conditioning   (these three: all or none; GPModel.eks)
+    double* pcovs;         // (T, N, Do, Do)  P- of every step, or null
+    double* cross;         // (T, N, Do, Do)  A_t P_{t-1}: row i is b[] of C1, or null
     int N, T, M, D, Do, Dy, tri;
 };
 
@@ -130,7 +133,9 @@ struct EkfLane {
     LogProd lp;
 };
 
-template <int NBLK, int RB, int DK>
+// EMIT: the form behind GPModel.eks, which also stores cross, pmeans and pcovs (a compile-time flag: the stores cost the plain
+// form up to 4 VGPRs and 31 spilled SGPRs as a run-time branch, and GPModel.ekf 0.2 % -- profiles/gp_eks/README.md)
+template <int NBLK, int RB, int DK, bool EMIT>
 __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpEkfArgs a)
 {
     constexpr bool BREG = (RB == 1);                    // K^-1 rows of the wave in VGPRs (2 KS = 8 NBLK <= 56 registers)
@@ -417,6 +422,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
                     for (int q = 0; q < 16; ++q) b[q] = fma(aik, pk[q], b[q]);
                 }
                 __builtin_amdgcn_wave_barrier();        // the chain's 16 lanes have read P before one of them writes it
+                const bool st = act && (c0 + n < N);
+                const int64_t o = (int64_t(t) * N + lc[k2]) * Do + i;
+                if (EMIT && st) {                       // A_t P_{t-1} for the smoother: its transpose is Cov(x_{t-1}, x_t | y_{0..t-1})
+                    double* cr = a.cross + o * Do;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if (q < Do) cr[q] = b[q];
+                }
 
                 // C2: the lower triangle of A P A^T + diag, mirrored
                 const int jend = act ? i : -1;
@@ -440,6 +453,13 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
                 double pr[16];
 #pragma unroll
                 for (int q = 0; q < 16; ++q) pr[q] = Pn[i * PD + q];
+                if (EMIT && st) {                       // the predicted moments, before conditioning
+                    a.pmeans[o] = mi;
+                    double* pc = a.pcovs + o * Do;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if (q < Do) pc[q] = pr[q];
+                }
 #pragma unroll 1
                 for (int j = 0; j < Dy; ++j) {
                     const double* rj = Pn + j * PD;
@@ -468,8 +488,7 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
 
                 // the stores and the next scaled GP input
                 if (act) {
-                    if (c0 + n < N) {
-                        const int64_t o = (int64_t(t) * N + lc[k2]) * Do + i;
+                    if (st) {
                         a.means[o] = mi;
                         double* cv = a.covs + o * Do;
 #pragma unroll
@@ -502,7 +521,7 @@ int launch_gp_ekf_k(const GpEkfArgs& a, hipStream_t st)
 {
     typedef GpBwdCfg<NBLK> C;
     const size_t lds = size_t(GpEkfGeom<NBLK, DK>::LDS_DOUBLES) * sizeof(double);
-    auto k = gp_ekf_kernel<NBLK, C::RB, DK>;
+    auto k = a.pcovs ? gp_ekf_kernel<NBLK, C::RB, DK, true> : gp_ekf_kernel<NBLK, C::RB, DK, false>;
     int rc = set_lds(k, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(k, dim3(unsigned((a.N + 15) / 16)), dim3(64 * C::W), lds, st, a);

@@ -302,6 +302,43 @@ int cbfssm_gp_ekf_f64(const cbfssm_pack_layout* layout, const double* pack, cons
                       void* stream);                                     /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
 
 /*
+ * ---- Rauch-Tung-Striebel smoother behind that filter: the posterior of every state given ALL observations of its chain.
+ * The forward pass is cbfssm_gp_ekf_f64 itself (means, covs, loglik bitwise its results) and leaves in addition
+ *
+ *   pmeans[t][n] = m-_t,  pcovs[t][n] = P-_t (before conditioning),  cross[t][n] = A_t P_{t-1}  (P_{-1} = P0)
+ *
+ * then, for t = T-1 .. 0 from (ms_{T-1}, Ps_{T-1}) = (means[T-1], covs[T-1]) copied bitwise:
+ *
+ *       G_t      = cross[t]^T (P-_t)^-1                  a Cholesky factorisation of P-_t and two triangular solves
+ *       ms_{t-1} = m_{t-1} + G_t (ms_t - m-_t)
+ *       Ps_{t-1} = P_{t-1} + G_t (Ps_t - P-_t) G_t^T     lower triangle computed and mirrored: bitwise symmetric
+ *       lag1[t]  = G_t Ps_t = Cov(x_{t-1}, x_t | y)      when lag1 is not NULL
+ *
+ * with (m_{t-1}, P_{t-1}) the filtered moments and (m0, P0) at t = 0, so the last iteration gives the smoothed initial
+ * belief (sm_init, sP_init).
+ *
+ * cbfssm_gp_eks_f64 (gp_tf.py:132-161, cbfssm.py:199-221,245-251): the inputs of cbfssm_gp_ekf_f64 -> means, covs, loglik
+ * as there; pmeans (T, N, Do), pcovs, cross (T, N, Do, Do); smeans (T, N, Do), scovs (T, N, Do, Do), sm_init (N, Do),
+ * sP_init (N, Do, Do), lag1 (T, N, Do, Do) or NULL, info (N) doubles: every entry written once.  info[n] = 0, or t + 1
+ * where a pivot of the factorisation of P-_t was <= 0 or not finite (the largest such t; P-_t is positive definite
+ * whenever P0 is positive semi-definite and fvar + var_x > 0): that chain's smeans, scovs at times < t, sm_init, sP_init and
+ * lag1[<= t] are then NaN, its results at times >= t and every other chain are unaffected, nothing traps.  Four launches on
+ * one stream: the alpha pre-kernel (`work`: cbfssm_gp_eks_work_elems doubles), the filter kernel, the gains G_t in
+ * parallel over (t, n) -- kept in the output slots of time t - 1 until the sweep has used them -- and the sweep, serial in
+ * time, one wave per four chains.  No atomics, no allocation, no host synchronisation, two calls are bitwise identical, and the results of a
+ * chain do not depend on the other chains of the call; nothing is launched (and nothing written) at N = 0 or T = 0.  Limits
+ * and refusals as cbfssm_gp_ekf_f64, the limits first: -3; NULL layout, pack, m0, y, var_y, work or any output but lag1,
+ * NULL a with D > Do, or N, T, Dy < 0: -1.  The count is host arithmetic in 64 bits and returns -1 for a bad layout.
+ */
+int64_t cbfssm_gp_eks_work_elems(const cbfssm_pack_layout* layout);      /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
+int cbfssm_gp_eks_f64(const cbfssm_pack_layout* layout, const double* pack, const double* m0, const double* P0,
+                      const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                      int Dy, int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans,
+                      double* pcovs, double* cross, double* smeans, double* scovs, double* sm_init, double* sP_init,
+                      double* lag1, double* info, double* work,
+                      void* stream);                                     /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
+
+/*
  * ---- differentiable GP rollout: the time loop of ONE sparse GP with per-chain inputs, and its adjoint.
  * Replaces the loop bodies of Voliro's recognition run (cbfssm/model/voliro.py:139-186: one run from h = 0, backwards in
  * time, GP input (h, u_t, y_t) with a per-particle u_t) and of the free-running transition of a trained CBF-SSM
