@@ -795,6 +795,162 @@ def gp_eks_eval(pack, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):
     return EksResult(smeans, scovs, loglik, means, covs, pmeans, pcovs, sm_init, sP_init, lag1, info.to(torch.int64))
 
 
+# ---- the differentiable form of gp_ekf_eval: the marginal likelihood of a GP state-space model as a training objective ---
+#
+#     means, covs, loglik = gp_ekf(pack, m0, P0, a, y, var_x, var_y, zeta_pos, zeta_mean, zeta_var_unc, variance_unc,
+#                                  lengthscales_unc, cond=None)
+#
+# Values: those of gp_ekf_eval on the prepared pack, bitwise (cbfssm_gp_ekf_save_f64, which also leaves m-, P-, A P and the
+# Jacobian J of every step).  Backward: cbfssm_gp_ekf_bwd_f64 -> cbfssm_reduce_partials_f64 -> cbfssm_gp_tail_f64
+# (kl_weight 0); gradients for m0, P0, a, y, var_x, var_y and the five parameter tensors, none for cond.  Conventions:
+#   P0     only its lower triangle is read: the gradient is that of the function of tril(P0) + tril(P0, -1)^T, exactly zero
+#          above the diagonal, a strictly lower entry carries both symmetric contributions
+#   None   P0, var_x, a given as None have no gradient
+#   y      exactly 0 where cond = 0 (by select: y may be NaN there); cond = 0 everywhere: zero gradients for y and var_y
+#   all three outputs take cotangents; an unused output costs nothing; the covs cotangent need not be symmetric
+# Once differentiable, float64, diagonal q(z), no host synchronisation, nothing launched without a chain or a step; the
+# call keeps a copy of the prepared pack, as gp_predict does.
+
+def _ekf_args(pack, m0, P0, a, y, var_x, var_y, cond):
+    dev = pack.buf.device
+    Do, Da = pack.Do, pack.D - pack.Do
+    if Da < 0:
+        raise ValueError('gp_ekf: the GP input dimension %d is smaller than its output dimension %d' % (pack.D, pack.Do))
+    f64 = lambda t: torch.as_tensor(t, dtype=torch.float64, device=dev)
+    y, m0, var_y = f64(y), f64(m0), f64(var_y)
+    assert y.dim() == 3 and m0.dim() == 2 and m0.shape == (y.shape[1], Do), 'y (T, N, Dy), m0 (N, Do)'
+    T, N, Dy = y.shape
+    if not 1 <= Dy <= Do:
+        raise ValueError('gp_ekf: y observes the first Dy state dimensions, 1 <= Dy <= %d (got %d)' % (Do, Dy))
+    assert tuple(var_y.shape) == (Dy,), 'var_y (Dy)'
+    if P0 is not None:
+        P0 = f64(P0)
+        assert tuple(P0.shape) == (N, Do, Do), 'P0 (N, Do, Do)'
+    if Da == 0:
+        assert a is None or tuple(a.shape) == (T, N, 0), 'a: None or (T, N, 0) when the GP takes the state alone'
+        a = None
+    else:
+        a = f64(a)
+        assert tuple(a.shape) == (T, N, Da), 'a (T, N, D - Do)'
+    if var_x is not None:
+        var_x = f64(var_x)
+        assert tuple(var_x.shape) == (Do,), 'var_x (Do)'
+    if cond is not None:
+        cond = torch.as_tensor(cond, device=dev)
+        assert tuple(cond.shape) == (T, N), 'cond (T, N)'
+        cond = (cond != 0).to(torch.float64).contiguous()
+    return m0, P0, a, y, var_x, var_y, cond
+
+
+class _GpEkf(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, cond, m0, P0, a, y, var_x, var_y, *params):
+        lib = _l.load()
+        pflat, cflat = _gp_flat(params)
+        det = lambda t: t.detach().contiguous() if t is not None else None
+        m0d, P0d, ad, yd, vxd, vyd = (det(t) for t in (m0, P0, a, y, var_x, var_y))
+        T, N, Dy = yd.shape
+        lay, dev, Do = pack.layout, yd.device, pack.Do
+        new = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)
+        means, covs = new(T, N, Do), new(T, N, Do, Do)
+        ctx.empty = (N == 0 or T == 0)
+        ctx.set_materialize_grads(False)                # an unused output reaches backward as None, and the entry point as NULL
+        ctx.layout, ctx.pflat, ctx.cflat = lay, pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in params)
+        ctx.has = (P0d is not None, ad is not None, vxd is not None, cond is not None)
+        ctx.dims = (T, N, Dy)
+        if ctx.empty:                                   # (no chain or no step: nothing is prepared or launched)
+            ctx.buf = None
+            ctx.save_for_backward(m0d, yd, vyd)
+            return means, covs, torch.zeros(N, dtype=torch.float64, device=dev)
+        _gp_prepare(pack, params, cflat)
+        buf = pack.buf.clone()
+        loglik = new(N)
+        pmeans, pcovs, cross, jac = new(T, N, Do), new(T, N, Do, Do), new(T, N, Do, Do), new(T, N, Do, Do)
+        nwork = int(lib.cbfssm_gp_ekf_work_elems(C.byref(lay)))
+        if nwork < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_ekf_work_elems refused the layout')
+        work = new(nwork)
+        _l.check(lib.cbfssm_gp_ekf_save_f64(C.byref(lay), _ptr(buf), _ptr(m0d), _ptr(P0d), _ptr(ad), _ptr(yd), _ptr(cond),
+                                            _ptr(vxd), _ptr(vyd), Dy, N, T, _ptr(means), _ptr(covs), _ptr(loglik),
+                                            _ptr(pmeans), _ptr(pcovs), _ptr(cross), _ptr(jac), _ptr(work), _stream()),
+                 'cbfssm_gp_ekf_save_f64')
+        ctx.buf = buf
+        ctx.save_for_backward(m0d, yd, vyd, means, covs, pmeans, pcovs, cross, jac,
+                              *[t for t in (P0d, ad, vxd, cond) if t is not None])           # (means, covs are outputs)
+        return means, covs, loglik
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gmeans, gcovs, gloglik):
+        lib = _l.load()
+        lay, buf = ctx.layout, ctx.buf
+        need = ctx.needs_input_grad                     # 2 m0, 3 P0, 4 a, 5 y, 6 var_x, 7 var_y, 8.. the leaves
+        T, N, Dy = ctx.dims
+        m0, y, var_y = ctx.saved_tensors[:3]
+        dev, Do = y.device, lay.Do
+        hasP, hasa, hasvx, hascond = ctx.has
+        if ctx.empty:
+            z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+            gp = _gp_split(torch.zeros_like(ctx.pflat), ctx.shapes, need[8:])
+            return (None, None, z(N, Do) if need[2] else None, z(N, Do, Do) if need[3] and hasP else None,
+                    z(T, N, lay.D - Do) if need[4] and hasa else None, z(T, N, Dy) if need[5] else None,
+                    z(Do) if need[6] and hasvx else None, z(Dy) if need[7] else None) + gp
+        means, covs, pmeans, pcovs, cross, jac = ctx.saved_tensors[3:9]
+        rest = list(ctx.saved_tensors[9:])
+        P0 = rest.pop(0) if hasP else None
+        a = rest.pop(0) if hasa else None
+        var_x = rest.pop(0) if hasvx else None
+        cond = rest.pop(0) if hascond else None
+        con = lambda t: t.contiguous() if t is not None else None
+        gmeans, gcovs, gloglik = con(gmeans), con(gcovs), con(gloglik)
+        gm0, gy = torch.empty_like(m0), torch.empty_like(y)
+        gP0 = torch.empty(N, Do, Do, dtype=torch.float64, device=dev) if need[3] and hasP else None
+        ga = torch.empty_like(a) if hasa else None
+        nwg = int(lib.cbfssm_gp_ekf_bwd_workgroups(C.byref(lay), N))
+        nwork = int(lib.cbfssm_gp_ekf_bwd_work_elems(C.byref(lay), N, T))
+        if nwg < 1 or nwork < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_ekf_bwd_workgroups / _work_elems refused the layout')
+        gpart = torch.empty((nwg + 32) * lay.rev_slab, dtype=torch.float64, device=dev)     # (+ CBFSSM_REDUCE_SPLIT)
+        work = torch.empty(nwork, dtype=torch.float64, device=dev)
+        image = torch.empty(lay.NBLK * lay.NBLK * 256, dtype=torch.float64, device=dev) if lay.rev_stash else None
+        _l.check(lib.cbfssm_gp_ekf_bwd_f64(C.byref(lay), _ptr(buf), _ptr(m0), _ptr(P0), _ptr(a), _ptr(y), _ptr(cond),
+                                           _ptr(var_x), _ptr(var_y), Dy, _ptr(means), _ptr(covs), _ptr(pmeans), _ptr(pcovs),
+                                           _ptr(cross), _ptr(jac), _ptr(gmeans), _ptr(gcovs), _ptr(gloglik), N, T, _ptr(gm0),
+                                           _ptr(gP0), _ptr(ga), _ptr(gy), _ptr(gpart), _ptr(work), _ptr(image), _stream()),
+                 'cbfssm_gp_ekf_bwd_f64')
+        gvx = gvy = None
+        gp = (None,) * 5
+        if need[6] or need[7] or any(need[8:]):
+            red = torch.empty(lay.rev_slab, dtype=torch.float64, device=dev)
+            _l.check(lib.cbfssm_reduce_partials_f64(_ptr(gpart), lay.rev_slab, nwg, _ptr(red), _stream()),
+                     'cbfssm_reduce_partials_f64')
+            small = lay.rev_slab - 192                  # the slab's scalars: [0, 16) d/d var_x, [16, 32) d/d var_y by state dim
+            gvx = red[small:small + Do].clone()
+            gvy = red[small + 16:small + 16 + Dy].clone()
+            if any(need[8:]):
+                gp = _gp_split(_gp_tail(lay, buf, red, image, 0.0, ctx.pflat, ctx.cflat), ctx.shapes, need[8:])
+        return (None, None, gm0 if need[2] else None, gP0, ga if need[4] and hasa else None, gy if need[5] else None,
+                gvx if need[6] and hasvx else None, gvy if need[7] else None) + gp
+
+
+def gp_ekf(pack, m0, P0, a, y, var_x, var_y, *params, cond=None):
+    """(means (T, N, Do), covs (T, N, Do, Do), loglik (N)): the values of gp_ekf_eval, bitwise, with a grad_fn into m0, P0,
+    a, y, var_x, var_y and the five parameter tensors when grad is enabled and one of them requires it; otherwise the pack
+    is prepared from the parameters and gp_ekf_eval runs: no records, no copy of the pack.  Arguments as gp_ekf_eval; the
+    gradient conventions (P0's lower triangle, None arguments, y and var_y under the mask, cotangents) stand above this
+    function."""
+    m0, P0, a, y, var_x, var_y, cond = _ekf_args(pack, m0, P0, a, y, var_x, var_y, cond)
+    params = _gp_args(pack, params)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [m0, P0, a, y, var_x, var_y] + params)):
+        if y.shape[0] * y.shape[1]:                     # (nothing is prepared or launched without a chain or a step)
+            pflat, cflat = _gp_flat(params)
+            _gp_prepare(pack, params, cflat)
+        return gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond)
+    return _GpEkf.apply(pack, cond, m0, P0, a, y, var_x, var_y, *params)
+
+
 # ---- the filter loop of one sparse GP: the rollout with a Gaussian filter update per step and chain behind a mask --------
 #
 #     traj, kl = gp_filter(pack, h0, a, ytilde, eps, var_x, var_y, zeta_pos, zeta_mean, zeta_var_unc, variance_unc,

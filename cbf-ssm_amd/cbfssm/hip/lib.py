@@ -43,6 +43,7 @@ SYMBOLS = (
     'cbfssm_gp_linearize_work_elems', 'cbfssm_gp_linearize_f64',
     'cbfssm_gp_ekf_work_elems', 'cbfssm_gp_ekf_f64',
     'cbfssm_gp_eks_work_elems', 'cbfssm_gp_eks_f64',
+    'cbfssm_gp_ekf_save_f64', 'cbfssm_gp_ekf_bwd_workgroups', 'cbfssm_gp_ekf_bwd_work_elems', 'cbfssm_gp_ekf_bwd_f64',
 )
 
 
@@ -205,6 +206,12 @@ def load():
     lib.cbfssm_gp_eks_work_elems.restype = i64
     lib.cbfssm_gp_eks_work_elems.argtypes = [C.POINTER(PackLayout)]
     lib.cbfssm_gp_eks_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 14
+    lib.cbfssm_gp_ekf_save_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 9
+    lib.cbfssm_gp_ekf_bwd_workgroups.restype = i64
+    lib.cbfssm_gp_ekf_bwd_workgroups.argtypes = [C.POINTER(PackLayout), i64]
+    lib.cbfssm_gp_ekf_bwd_work_elems.restype = i64
+    lib.cbfssm_gp_ekf_bwd_work_elems.argtypes = [C.POINTER(PackLayout), i64, i64]
+    lib.cbfssm_gp_ekf_bwd_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip] + [vp] * 9 + [i64, i64] + [vp] * 8
     for name in ('cbfssm_gp_rollout_partials', 'cbfssm_gp_rollout_bwd_workgroups'):
         getattr(lib, name).restype = i64
         getattr(lib, name).argtypes = [C.POINTER(PackLayout), i64]

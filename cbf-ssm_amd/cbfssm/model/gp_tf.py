@@ -35,7 +35,10 @@ around a learned transition).  Both are evaluation only and for the diagonal q(z
 over the GP as a transition -- per chain a mean and a full state covariance propagated through m = h + fmean, conditioned
 on observations of the first Dy state dimensions where `cond` says so (cbfssm/model/cbfssm.py:199-221,245-251) -- with the
 log-likelihood of each chain, as one fused launch.  cond = 0 everywhere is a deterministic multi-step forecast with its
-covariances.  Evaluation only, diagonal q(z).
+covariances.  Diagonal q(z).  Evaluation only by default; `ekf(..., differentiable=True)` gives means, covs and loglik a
+grad_fn into m0, P0, a, y, var_x, var_y and the five parameter tensors (one fused adjoint launch over the whole time loop,
+cbfssm.hip.autograd.gp_ekf): -loglik.sum() is the marginal likelihood of the GP state-space model as a training objective,
+with no particles and no sampling noise.
 `GPModel.eks(..., lag_one=False)` is that filter followed by the Rauch-Tung-Striebel sweep: smoothed and one-step predictive
 moments, the smoothed initial belief and, on request, the lag-one cross-covariances (the E-step of EM), in four launches.
 """
@@ -351,7 +354,7 @@ class GPModel:
         pack = self._prepared() if Xnew.shape[0] else self._pack                 # (nothing runs without a point)
         return _ag.gp_linearize_eval(pack, Xnew, variance=variance)
 
-    def ekf(self, m0, P0, a, y, var_x, var_y, cond=None):
+    def ekf(self, m0, P0, a, y, var_x, var_y, cond=None, differentiable=False):
         """An addition to the reference's surface: the extended Kalman filter over this GP as the transition of CBF-SSM
         (cbfssm/model/cbfssm.py:199-221) with its observation model (cbfssm.py:245-251: the first Dy state dimensions plus
         N(0, diag(var_y))) -- a Gaussian belief per chain, mean and full covariance, as one launch:
@@ -371,10 +374,20 @@ class GPModel:
         everywhere): zeros mark missing observations -- y may hold NaN there, it is never read into a result -- and
         cond = 0 everywhere is uncertainty propagation, a multi-step forecast with its covariances, loglik exactly 0.
         Returns (means (T, N, out_dim), covs (T, N, out_dim, out_dim), loglik (N)); every covs[t, n] is bitwise symmetric.
-        Evaluation only: the results carry no grad_fn whatever the leaves or the inputs ask for.  Raises ValueError on a
-        q_full=True model."""
+        By default evaluation only: the results carry no grad_fn whatever the leaves or the inputs ask for.
+
+        differentiable=True: when a leaf, m0, P0, a, y, var_x or var_y requires grad, the same values (bitwise) carry a
+        grad_fn (cbfssm.hip.autograd.gp_ekf: one fused adjoint launch over the whole time loop), so -loglik.sum() is a
+        training objective free of sampling noise.  All three results take cotangents (the one for covs need not be
+        symmetric); once differentiable; cond gets no gradient.  Conventions: the gradient for P0 is that of the function
+        of tril(P0) + tril(P0, -1)^T -- exactly zero above the diagonal, a strictly lower entry carries both symmetric
+        contributions; an argument given as None (P0, var_x, a) has no gradient; the gradient for y is exactly 0 where
+        cond = 0 (y may be NaN there), and with cond = 0 everywhere those for y and var_y are zero tensors.  `eks` stays
+        evaluation only.  Raises ValueError on a q_full=True model and when in_dim < out_dim."""
         self._no_full_q('ekf')
         from ..hip import autograd as _ag
+        if differentiable and self._wants_grad(m0, P0, a, y, var_x, var_y):
+            return _ag.gp_ekf(self._pack, m0, P0, a, y, var_x, var_y, *self.parameters(), cond=cond)
         y = _f64(y, self.zeta_pos.device)
         pack = self._prepared() if y.shape[0] * y.shape[1] else self._pack       # (nothing runs without a chain or a step)
         return _ag.gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond)

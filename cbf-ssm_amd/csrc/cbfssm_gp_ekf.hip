@@ -61,11 +61,12 @@ int gp_ekf_check_sizes(const char* who, const cbfssm_pack_layout* L, int Dy, int
     return 0;
 }
 
-// the alpha pre-kernel and the filter launch; pmeans, pcovs, cross: all three or none (the smoother's inputs)
-int gp_ekf_launch(const char* who, const cbfssm_pack_layout* L, const double* pack, const double* m0, const double* P0,
-                  const double* a, const double* y, const double* cond, const double* var_x, const double* var_y, int Dy,
-                  int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans, double* pcovs,
-                  double* cross, double* work, hipStream_t st)
+// the alpha pre-kernel and the filter launch; pmeans, pcovs, cross: all three or none (the smoother's inputs); jac: with
+// those three, the forward under grad
+static int gp_ekf_launch_j(const char* who, const cbfssm_pack_layout* L, const double* pack, const double* m0, const double* P0,
+                           const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                           int Dy, int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans,
+                           double* pcovs, double* cross, double* jac, double* work, hipStream_t st)
 {
     const int tri = (L->gp_form == CBFSSM_GP_FORM_TRI);
     hipLaunchKernelGGL(gp_lin_alpha_kernel, dim3(16), dim3(256), 0, st, pack + L->Kinv, pack + L->Linvt, pack + L->muB, L->M,
@@ -81,9 +82,19 @@ int gp_ekf_launch(const char* who, const cbfssm_pack_layout* L, const double* pa
     k.m0 = m0; k.P0 = P0; k.a = a; k.y = y; k.cond = cond; k.var_x = var_x; k.var_y = var_y; k.alpha = work;
     k.means = means; k.covs = covs; k.loglik = loglik; k.pmeans = pmeans; k.pcovs = pcovs; k.cross = cross;
     k.N = int(N); k.T = int(T); k.M = L->M; k.D = L->D; k.Do = L->Do; k.Dy = Dy; k.tri = tri;
+    k.jac = jac;
     int rc = dispatch_gp_ekf(L->NBLK, L->DK, k, st);
     if (rc) return fail(rc, "%s launch failed (NBLK=%d DK=%d rc=%d)", who, L->NBLK, L->DK, rc);
     return 0;
+}
+
+int gp_ekf_launch(const char* who, const cbfssm_pack_layout* L, const double* pack, const double* m0, const double* P0,
+                  const double* a, const double* y, const double* cond, const double* var_x, const double* var_y, int Dy,
+                  int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans, double* pcovs,
+                  double* cross, double* work, hipStream_t st)
+{
+    return gp_ekf_launch_j(who, L, pack, m0, P0, a, y, cond, var_x, var_y, Dy, N, T, means, covs, loglik, pmeans, pcovs, cross,
+                           nullptr, work, st);
 }
 
 }  // namespace cbfssm
@@ -108,6 +119,21 @@ int cbfssm_gp_ekf_f64(const cbfssm_pack_layout* L, const double* pack, const dou
     if (N == 0 || T == 0) return 0;
     return gp_ekf_launch("gp_ekf", L, pack, m0, P0, a, y, cond, var_x, var_y, Dy, N, T, means, covs, loglik, nullptr, nullptr,
                          nullptr, work, (hipStream_t)stream);
+}
+
+// the forward under grad: the filter alone (no smoother launches), leaving what cbfssm_gp_ekf_bwd_f64 reads
+int cbfssm_gp_ekf_save_f64(const cbfssm_pack_layout* L, const double* pack, const double* m0, const double* P0, const double* a,
+                           const double* y, const double* cond, const double* var_x, const double* var_y, int Dy, int64_t N,
+                           int64_t T, double* means, double* covs, double* loglik, double* pmeans, double* pcovs, double* cross,
+                           double* jac, double* work, void* stream)
+{
+    if (int rc = gp_ekf_check_sizes("gp_ekf_save", L, Dy, N, T)) return rc;
+    if (!pack || !m0 || !y || !var_y || !means || !covs || !loglik || !pmeans || !pcovs || !cross || !jac || !work)
+        return fail(-1, "null pointer");
+    if (L->D > L->Do && !a) return fail(-1, "null a with D > Do");
+    if (N == 0 || T == 0) return 0;
+    return gp_ekf_launch_j("gp_ekf_save", L, pack, m0, P0, a, y, cond, var_x, var_y, Dy, N, T, means, covs, loglik, pmeans,
+                           pcovs, cross, jac, work, (hipStream_t)stream);
 }
 
 }  // extern "C"

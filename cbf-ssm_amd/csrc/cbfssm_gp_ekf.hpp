@@ -59,6 +59,7 @@ struct GpEkfArgs {
     double* pcovs;         // (T, N, Do, Do)  P- of every step, or null
     double* cross;         // (T, N, Do, Do)  A_t P_{t-1}: row i is b[] of C1, or null
     int N, T, M, D, Do, Dy, tri;
+    double* jac;           // (T, N, Do, Do)  J[d][i] of every step, or null (with the three above: the forward under grad)
 };
 
 // LDS: xq | KJ | T1 | red0 | 1 / l | P | fm | fv.  KJ is the kernel tile [16 NBLK][17] and, once A2 exists, the Jacobian tile
@@ -135,7 +136,8 @@ struct EkfLane {
 
 // EMIT: the form behind GPModel.eks, which also stores cross, pmeans and pcovs (a compile-time flag: the stores cost the plain
 // form up to 4 VGPRs and 31 spilled SGPRs as a run-time branch, and GPModel.ekf 0.2 % -- profiles/gp_eks/README.md)
-template <int NBLK, int RB, int DK, bool EMIT>
+// SAVEJ: the form behind gp_ekf under grad, which stores the Jacobian tile as well (cbfssm_gp_ekf_bwd.hpp)
+template <int NBLK, int RB, int DK, bool EMIT, bool SAVEJ = false>
 __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpEkfArgs a)
 {
     constexpr bool BREG = (RB == 1);                    // K^-1 rows of the wave in VGPRs (2 KS = 8 NBLK <= 56 registers)
@@ -430,6 +432,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
                     for (int q = 0; q < 16; ++q)
                         if (q < Do) cr[q] = b[q];
                 }
+                if constexpr (SAVEJ) {
+                    if (st) {
+                        double* jc = a.jac + o * Do;
+#pragma unroll
+                        for (int q = 0; q < 16; ++q)
+                            if (q < Do) jc[q] = Jn[i * PD + q];
+                    }
+                }
 
                 // C2: the lower triangle of A P A^T + diag, mirrored
                 const int jend = act ? i : -1;
@@ -521,7 +531,8 @@ int launch_gp_ekf_k(const GpEkfArgs& a, hipStream_t st)
 {
     typedef GpBwdCfg<NBLK> C;
     const size_t lds = size_t(GpEkfGeom<NBLK, DK>::LDS_DOUBLES) * sizeof(double);
-    auto k = a.pcovs ? gp_ekf_kernel<NBLK, C::RB, DK, true> : gp_ekf_kernel<NBLK, C::RB, DK, false>;
+    auto k = a.jac ? gp_ekf_kernel<NBLK, C::RB, DK, true, true>
+                   : (a.pcovs ? gp_ekf_kernel<NBLK, C::RB, DK, true> : gp_ekf_kernel<NBLK, C::RB, DK, false>);
     int rc = set_lds(k, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(k, dim3(unsigned((a.N + 15) / 16)), dim3(64 * C::W), lds, st, a);

@@ -30,7 +30,8 @@
 // After phase G the state rows of gX plus Fm are the next carry (h enters m directly and through the GP).  sum Fv per
 // state dim goes to the slab's d/d var_x entries, sum rb to its d/d var_y entries.
 // (Phases B to F are a copy of the rollout adjoint's, which are a copy of the batch kernel's: the existing kernels keep
-// their code.)  No atomics, one writer per output: two calls are bitwise identical.  Padded chains carry zero adjoints
+// their code; gp_ekf_bwd_kernel, cbfssm_gp_ekf_bwd.hpp, is a further copy of B to G: a fix here belongs there too.)
+// No atomics, one writer per output: two calls are bitwise identical.  Padded chains carry zero adjoints
 // and the rows m >= M of the tiles are zero, so both contribute exactly zero.
 #pragma once
 #include "cbfssm_gp_bwd.hpp"

@@ -339,6 +339,45 @@ int cbfssm_gp_eks_f64(const cbfssm_pack_layout* layout, const double* pack, cons
                       void* stream);                                     /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
 
 /*
+ * ---- differentiable GPModel.ekf: what tf.gradients gives a graph that builds the filter above from gp.predict and its
+ * Jacobian (gp_tf.py:132-161 differentiated twice in the inputs; cbfssm.py:199-221,245-251), as one adjoint launch.
+ *
+ * cbfssm_gp_ekf_save_f64: the forward under grad.  cbfssm_gp_ekf_f64 (means, covs, loglik bitwise its results; `work`:
+ * cbfssm_gp_ekf_work_elems doubles) which also leaves pmeans (T, N, Do), pcovs, cross (T, N, Do, Do) as cbfssm_gp_eks_f64
+ * does, and jac (T, N, Do, Do): J_t[d][i] = d fmean[d] / d x[i] at the input of step t.  No smoother launches.  Refusals as
+ * cbfssm_gp_ekf_f64; the four records may not be NULL.
+ *
+ * cbfssm_gp_ekf_bwd_f64: the adjoint.  pack, m0, P0, a, y, cond, var_x, var_y, Dy as in the forward call; means .. jac as
+ * the forward left them; gmeans (T, N, Do), gcovs (T, N, Do, Do), gloglik (N): d loss / d means, covs, loglik, each may
+ * be NULL (zero); gcovs need not be symmetric.
+ *   -> gm0 (N, Do); gP0 (N, Do, Do) or NULL: the gradient of the function of tril(P0) + tril(P0, -1)^T, exactly zero above
+ *      the diagonal; ga (T, N, D - Do); gy (T, N, Dy), exactly 0 where cond = 0 (y may be NaN there);
+ *      gpart: cbfssm_gp_ekf_bwd_workgroups slabs of layout->rev_slab doubles ("Slab layout of the parameter adjoints of
+ *      one GP"; [0, Do) of its scalars: d / d var_x, [16, 16 + Dy): d / d var_y), with room for CBFSSM_REDUCE_SPLIT more;
+ *      work: cbfssm_gp_ekf_bwd_work_elems doubles (always needed); M > 112 (layout->rev_stash): gB_image
+ *      ([NBLK][NBLK][4][64], cleared and filled by cbfssm_stash_contract_f64; slot = workgroup * T + step, and one more
+ *      slot per workgroup behind them for alpha = K^-1 mu), else it may be NULL.
+ * One workgroup per 16 chains, no atomics, no spin waits; two calls are bitwise identical.  Nothing is launched at N = 0
+ * or T = 0.  Limits and refusals as cbfssm_gp_ekf_f64 (-3 before any launch: M, D, Do, D < Do, Dy, a layout without an
+ * adjoint slab); NULL layout, pack, m0, y, var_y, a record, gm0, gy, gpart or work, NULL a / ga with D > Do: -1.  The counts
+ * are host arithmetic in 64 bits and return -1 for a bad layout.
+ */
+int cbfssm_gp_ekf_save_f64(const cbfssm_pack_layout* layout, const double* pack, const double* m0, const double* P0,
+                           const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                           int Dy, int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans,
+                           double* pcovs, double* cross, double* jac, double* work,
+                           void* stream);                                /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
+int64_t cbfssm_gp_ekf_bwd_workgroups(const cbfssm_pack_layout* layout, int64_t N);              /* tf.gradients of the above */
+int64_t cbfssm_gp_ekf_bwd_work_elems(const cbfssm_pack_layout* layout, int64_t N, int64_t T);   /* tf.gradients of the above */
+int cbfssm_gp_ekf_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* m0, const double* P0,
+                          const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                          int Dy, const double* means, const double* covs, const double* pmeans, const double* pcovs,
+                          const double* cross, const double* jac, const double* gmeans, const double* gcovs,
+                          const double* gloglik, int64_t N, int64_t T, double* gm0, double* gP0, double* ga, double* gy,
+                          double* gpart, double* work, double* gB_image,
+                          void* stream);                                 /* tf.gradients of gp_tf.py:132-161, cbfssm.py:199-251 */
+
+/*
  * ---- differentiable GP rollout: the time loop of ONE sparse GP with per-chain inputs, and its adjoint.
  * Replaces the loop bodies of Voliro's recognition run (cbfssm/model/voliro.py:139-186: one run from h = 0, backwards in
  * time, GP input (h, u_t, y_t) with a per-particle u_t) and of the free-running transition of a trained CBF-SSM
