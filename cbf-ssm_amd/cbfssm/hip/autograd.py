@@ -6,7 +6,9 @@ recurrence with a masked Gaussian filter update per step (`gp_filter`) and the r
 to the inputs, all output dimensions in one launch; `gp_ekf_eval`, evaluation only as well, runs the extended Kalman filter
 those Jacobians are for -- a mean and a full state covariance per chain through time, conditioned where there are
 observations -- as one launch; `gp_eks_eval` adds the Rauch-Tung-Striebel sweep behind it: smoothed and one-step predictive
-moments, the smoothed initial belief and the lag-one cross-covariances.
+moments, the smoothed initial belief and the lag-one cross-covariances.  `gp_moment_match_eval`, evaluation only, gives the
+exact moments of the GP output under a Gaussian input -- mean, full output covariance, covariance with the input -- in one
+launch.
 
 The CBF-SSM loss:
 
@@ -655,6 +657,47 @@ def gp_linearize_eval(pack, X, variance=True):
         _l.check(lib.cbfssm_gp_linearize_f64(C.byref(lay), _ptr(pack.buf), _ptr(X), n, _ptr(fmean), _ptr(fvar), _ptr(dmean),
                                              _ptr(dvar), _ptr(work), _stream()), 'cbfssm_gp_linearize_f64')
     return fmean, fvar, dmean, dvar
+
+
+# ---- exact Gaussian moments of one sparse GP under a Gaussian input: moment matching ---------------------------------------
+#
+#     fmean, fcov, xcov, info = gp_moment_match_eval(pack, mean, cov, cross=True)
+#
+# for x ~ N(mean[n], cov[n]) and the posterior of gp_tf.py:132-161: E[f], Cov(f, f) with the correlation between output
+# dimensions that the shared uncertain input brings, Cov(f, x) -- closed form for the RBF kernel, one launch
+# (cbfssm_gp_moment_match_f64: per point two D x D Cholesky factorisations, the M x M matrix of expected kernel products as
+# register tiles) instead of an (npts, M, M) intermediate in the tensor library.
+
+def gp_moment_match_eval(pack, mean, cov, cross=True):
+    """(fmean (npts, Do), fcov (npts, Do, Do), xcov (npts, Do, D) or None, info (npts) int64) on a pack that is already
+    prepared.  mean (npts, D); cov (npts, D, D), only the lower triangle is read, or None (zero: predict, with xcov = 0).
+    cross=False leaves xcov out; the other results are bitwise those of the full call.  info[n] != 0: cov[n] is not
+    positive semi-definite and the results of point n are NaN.  Evaluation only: no grad_fn, nothing is launched without
+    a point; reading info as int64 is a device-side cast, not a host synchronisation."""
+    lib = _l.load()
+    lay, dev = pack.layout, pack.buf.device
+    mean = torch.as_tensor(mean, dtype=torch.float64, device=dev)
+    assert mean.dim() == 2 and mean.shape[1] == pack.D, 'mean (npts, D)'
+    n, D, Do = mean.shape[0], pack.D, pack.Do
+    if cov is not None:
+        cov = torch.as_tensor(cov, dtype=torch.float64, device=dev)
+        assert tuple(cov.shape) == (n, D, D), 'cov (npts, D, D)'
+    with torch.no_grad():
+        mean = mean.detach().contiguous()
+        cov = cov.detach().contiguous() if cov is not None else None
+        fmean = torch.empty(n, Do, dtype=torch.float64, device=dev)
+        fcov = torch.empty(n, Do, Do, dtype=torch.float64, device=dev)
+        xcov = torch.empty(n, Do, D, dtype=torch.float64, device=dev) if cross else None
+        info = torch.empty(n, dtype=torch.float64, device=dev)
+        if n == 0:
+            return fmean, fcov, xcov, info.to(torch.int64)
+        nwork = int(lib.cbfssm_gp_moment_match_work_elems(C.byref(lay)))
+        if nwork < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_moment_match_work_elems refused the layout')
+        work = torch.empty(nwork, dtype=torch.float64, device=dev)
+        _l.check(lib.cbfssm_gp_moment_match_f64(C.byref(lay), _ptr(pack.buf), _ptr(mean), _ptr(cov), n, _ptr(fmean), _ptr(fcov),
+                                                _ptr(xcov), _ptr(info), _ptr(work), _stream()), 'cbfssm_gp_moment_match_f64')
+    return fmean, fcov, xcov, info.to(torch.int64)
 
 
 # ---- the extended Kalman filter over the transition of one sparse GP: a Gaussian belief per chain through time -------------

@@ -41,6 +41,13 @@ cbfssm.hip.autograd.gp_ekf): -loglik.sum() is the marginal likelihood of the GP 
 with no particles and no sampling noise.
 `GPModel.eks(..., lag_one=False)` is that filter followed by the Rauch-Tung-Striebel sweep: smoothed and one-step predictive
 moments, the smoothed initial belief and, on request, the lag-one cross-covariances (the E-step of EM), in four launches.
+
+`GPModel.moment_match(mean, cov)` is the exact counterpart of `linearize` for a Gaussian input x ~ N(mean, cov): E[f], the
+full output covariance Cov(f, f) and Cov(f, x) in closed form for the RBF kernel (the moment matching of PILCO and of the GP
+assumed-density filter), right where the belief is as wide as a lengthscale and a first-order model is not -- one launch,
+the (N, M, M) matrix of expected kernel products never reaches memory.  `GPModel.transition_moments(h, P, a)` is the
+Gaussian one-step prediction of the recurrence on top of it: m+, P+ and Cov(h, h+).  Both are evaluation only and for the
+diagonal q(z).
 """
 import ctypes as C
 import numpy as np
@@ -208,7 +215,8 @@ class GPModel:
     branch of gp_tf.py:150-159).  The third leaf is then `zeta_sqrt` (Do, M, M), unconstrained, initialised to
     sqrt(zeta_var) I; only its lower triangle is read and its gradient above the diagonal is exactly zero.  `zeta_std`
     returns the factors L_d, `zeta_var` the marginal variances diag(L_d L_d^T) as (M, Do).  `rollout`, `filter`,
-    `linearize`, `transition_jacobians`, `ekf` and `eks` raise ValueError on such a model."""
+    `linearize`, `transition_jacobians`, `ekf`, `eks`, `moment_match` and `transition_moments` raise ValueError on such a
+    model."""
 
     def __init__(self, in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var, dtype='float64',
                  device=None, seed=None, q_full=False):
@@ -445,3 +453,68 @@ class GPModel:
         dmean = self.linearize(X, variance=False)[2]
         A = dmean[:, :, :Do] + torch.eye(Do, dtype=torch.float64, device=dev)
         return A, dmean[:, :, Do:].contiguous()
+
+    def moment_match(self, mean, cov, cross=True):
+        """An addition to the reference's surface: the exact moments of the GP output under a Gaussian input
+        x[n] ~ N(mean[n], cov[n]) -- the moment matching of PILCO and of the GP assumed-density filter, closed form for the
+        RBF kernel, where `linearize` is first order at the mean -- as one launch:
+
+            fmean[n, d]    = E[f_d]                                       (N, out_dim)
+            fcov[n, d, e]  = Cov(f_d, f_e)                                (N, out_dim, out_dim), bitwise symmetric
+            xcov[n, d, i]  = Cov(f_d, x_i)                                (N, out_dim, in_dim), dmean's layout
+
+        with f_d | x ~ N(fmean_d(x), fvar_d(x)) of `predict`, independent over d given x: diag fcov = E[fvar] + Var[fmean],
+        and the off-diagonal is the correlation that sharing the uncertain input brings.  mean (N, in_dim); cov
+        (N, in_dim, in_dim), only the lower triangle is read, or None (zero).  cov need only be positive semi-definite --
+        zero blocks, rank one and cov = 0 are ordinary inputs; cov = 0 gives `predict` back (diag fcov = fvar) and xcov
+        exactly zero.  Returns (fmean, fcov, xcov, info); cross=False leaves xcov out (None; the other results are bitwise
+        the same).  info (N) int64 is 0, or 1 / 2 where cov[n] is not positive semi-definite (a non-positive pivot in the
+        first / second factorisation): the results of that point are NaN and nothing else is affected.  Evaluation only:
+        the results carry no grad_fn whatever the leaves or the inputs ask for.  Raises ValueError on a q_full=True model."""
+        self._no_full_q('moment_match')
+        from ..hip import autograd as _ag
+        dev = self.zeta_pos.device
+        mean = _f64(mean, dev)
+        assert mean.dim() == 2 and mean.shape[1] == self.in_dim, 'mean (N, in_dim)'
+        if cov is not None:
+            cov = _f64(cov, dev)
+            assert tuple(cov.shape) == (mean.shape[0], self.in_dim, self.in_dim), 'cov (N, in_dim, in_dim)'
+        pack = self._prepared() if mean.shape[0] else self._pack                 # (nothing runs without a point)
+        return _ag.gp_moment_match_eval(pack, mean, cov, cross=cross)
+
+    def transition_moments(self, h, P, a=None):
+        """The Gaussian one-step prediction of the recurrence `rollout`, `filter` and `ekf` run, h+ = h + f(concat(h, a)),
+        for a belief h ~ N(h[n], P[n]) and a known input a (input covariance blockdiag(P, 0)), by `moment_match`:
+
+            C  = Cov(h, f) = xcov[:, :, :out_dim]^T
+            m+ = h + fmean;   P+ = P + C + C^T + fcov;   cross = P + C = Cov(h, h+)      (what a smoother gain needs)
+
+        h (N, out_dim), P (N, out_dim, out_dim) of which only the lower triangle is read, a (N, in_dim - out_dim) or None
+        when the GP takes the state alone.  Returns (m+, P+, cross, info); P+ is bitwise symmetric; the process noise var_x
+        is the caller's to add; info as in `moment_match`.  Evaluation only.  Raises ValueError on a q_full=True model and
+        when in_dim < out_dim."""
+        self._no_full_q('transition_moments')
+        Do, Da = self.out_dim, self.in_dim - self.out_dim
+        if Da < 0:
+            raise ValueError('transition_moments: the GP input dimension %d is smaller than its output dimension %d'
+                             % (self.in_dim, self.out_dim))
+        dev = self.zeta_pos.device
+        h, P = _f64(h, dev), _f64(P, dev)
+        assert h.dim() == 2 and h.shape[1] == Do, 'h (N, out_dim)'
+        assert tuple(P.shape) == (h.shape[0], Do, Do), 'P (N, out_dim, out_dim)'
+        Pl = torch.tril(P)
+        P = Pl + torch.tril(P, -1).transpose(1, 2)                               # the function of the lower triangle
+        if Da == 0:
+            assert a is None or tuple(a.shape) == (h.shape[0], 0), 'a: None or (N, 0) when the GP takes the state alone'
+            X, S = h, Pl
+        else:
+            a = _f64(a, dev)
+            assert tuple(a.shape) == (h.shape[0], Da), 'a (N, in_dim - out_dim)'
+            X = torch.cat([h, a], dim=1)
+            S = torch.zeros(h.shape[0], self.in_dim, self.in_dim, dtype=torch.float64, device=dev)
+            S[:, :Do, :Do] = Pl
+        fmean, fcov, xcov, info = self.moment_match(X, S)
+        Cm = xcov[:, :, :Do].transpose(1, 2)                                     # Cov(h, f)
+        low = torch.tril(P + Cm + Cm.transpose(1, 2) + fcov)
+        Pn = low + torch.tril(low, -1).transpose(1, 2)
+        return h + fmean, Pn, P + Cm, info

@@ -1,0 +1,2 @@
+#include "cbfssm_gp_mm.hpp"
+CBF_GPMM_INSTANTIATE(16)

@@ -265,6 +265,38 @@ int cbfssm_gp_linearize_f64(const cbfssm_pack_layout* layout, const double* pack
                             double* fmean, double* fvar, double* dmean, double* dvar, double* work, void* stream);
 
 /*
+ * ---- exact Gaussian moments of ONE sparse GP under a Gaussian input: for x ~ N(mean[n], cov[n]) and the posterior of
+ * GPModel.predict (gp_tf.py:132-161, diagonal q(z), RBF kernel) the mean of the output, its full covariance -- with the
+ * correlation between output dimensions that sharing the uncertain input brings -- and its covariance with the input, in
+ * closed form (the moment matching of PILCO and of the GP assumed-density filter): nothing is linearised or sampled.
+ *
+ *   fmean[n][d]   = E[f_d]           fcov[n][d][e] = Cov(f_d, f_e)  (npts, Do, Do)      xcov[n][d][i] = Cov(f_d, x_i)  (npts, Do, D)
+ *
+ * with f_d | x ~ N(fmean_d(x), fvar_d(x)) independent over d given x, as in predict: diag fcov = E[fvar] + Var[fmean], the
+ * off-diagonal is Cov[fmean_d, fmean_e].
+ *
+ * cbfssm_gp_moment_match_f64: pack prepared (diagonal q(z)); mean (npts, D), cov (npts, D, D) of which only the lower triangle
+ *   is read, NULL = zero -> fmean (npts, Do), fcov, info (npts) and, when the pointer is not NULL, xcov; without it the other
+ *   results are bitwise the same.  cov need only be positive semi-definite: the two matrices that are factorised, I + S~ and
+ *   I / 2 + S~ (S~ = cov in lengthscale units), are positive definite then, so zero blocks, rank one and cov = 0 are ordinary
+ *   inputs; cov = 0 gives predict back and xcov exactly zero.  A non-positive pivot sets info[n] = 1 (first factor) or 2
+ *   (second) and makes the three results of that point NaN; nothing else is affected.  fcov[n] is bitwise symmetric.
+ *   Two pre-kernels form alpha = K^-1 mu (in the order layout->gp_form asks for, as cbfssm_gp_linearize_f64) and the tiles of
+ *   W_d = K^-1 - K^-1 diag(zeta_var[:, d]) K^-1 (dense K^-1 in both forms, f64 MFMA) in `work`
+ *   (cbfssm_gp_moment_match_work_elems doubles), then ONE launch does the rest: per point the two D x D Cholesky
+ *   factorisations in registers, and the M x M matrix Q of expected kernel products as 16 x 16 tiles that never leave the
+ *   registers -- the point-dependent part of its exponent is a Gram product on the f64 MFMA units, as is its contraction
+ *   with alpha.  Persistent workgroups of 16 points, at most as many as cbfssm_gp_predict_bwd_workgroups names.
+ * No atomics, no allocation, no host synchronisation, every output entry has one writer, two calls are bitwise identical,
+ * and the results of a point do not depend on the other points of the call; nothing is launched at npts = 0.  Limits as
+ * cbfssm_gp_predict_f64 (M <= 320, D <= 24, Do <= 16), else -3 before any launch; NULL layout, pack, mean, fmean, fcov, info
+ * or work, or npts < 0: -1.  The count is host arithmetic in 64 bits and returns -1 for a bad layout.
+ */
+int64_t cbfssm_gp_moment_match_work_elems(const cbfssm_pack_layout* layout);      /* gp_tf.py:132-161 */
+int cbfssm_gp_moment_match_f64(const cbfssm_pack_layout* layout, const double* pack, const double* mean, const double* cov,
+                               int64_t npts, double* fmean, double* fcov, double* xcov, double* info, double* work, void* stream);
+
+/*
  * ---- extended Kalman filter over the transition of ONE sparse GP: a Gaussian belief (m, P) per chain, carried through
  * time by the local linear model above inside the recurrence of CBF-SSM (cbfssm/model/cbfssm.py:199-221) and conditioned
  * on observations of the first Dy state dimensions (cbfssm.py:245-251), y = x[:Dy] + N(0, diag(var_y)).  Forward in time,
