@@ -8,7 +8,8 @@ those Jacobians are for -- a mean and a full state covariance per chain through 
 observations -- as one launch; `gp_eks_eval` adds the Rauch-Tung-Striebel sweep behind it: smoothed and one-step predictive
 moments, the smoothed initial belief and the lag-one cross-covariances.  `gp_moment_match_eval`, evaluation only, gives the
 exact moments of the GP output under a Gaussian input -- mean, full output covariance, covariance with the input -- in one
-launch.
+launch; `gp_adf_eval` runs the assumed-density filter over them -- `gp_ekf_eval`'s recursion with the exact moments in place
+of the linearisation -- as one launch for all steps, and `gp_ads_eval` the smoother behind it.
 
 The CBF-SSM loss:
 
@@ -835,6 +836,121 @@ def gp_eks_eval(pack, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):
                                        _ptr(var_x), _ptr(var_y), Dy, N, T, _ptr(means), _ptr(covs), _ptr(loglik), _ptr(pmeans),
                                        _ptr(pcovs), _ptr(cross), _ptr(smeans), _ptr(scovs), _ptr(sm_init), _ptr(sP_init),
                                        _ptr(lag1), _ptr(info), _ptr(work), _stream()), 'cbfssm_gp_eks_f64')
+    return EksResult(smeans, scovs, loglik, means, covs, pmeans, pcovs, sm_init, sP_init, lag1, info.to(torch.int64))
+
+
+# ---- the assumed-density (moment-matching) filter over the transition of one sparse GP, and the smoother behind it ---------
+#
+#     res = gp_adf_eval(pack, m0, P0, a, y, var_x, var_y, cond=None)                          (an AdfResult)
+#     res = gp_ads_eval(pack, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False)           (an EksResult)
+#
+#     for t in 0..T-1:
+#         x = concat(m, a[t]);  S = blockdiag(P, 0)                                        (the auxiliary input is known)
+#         fmean, fcov, xcov = moment_match(x, S);  Cx = xcov[:, :Do]                       (exact, gp_moment_match_eval)
+#         m = m + fmean;  cross[t] = P + Cx;  P = P + Cx + Cx^T + fcov + diag(var_x);  pmeans[t], pcovs[t] = m, P
+#         where cond[t, n], for j in 0..Dy-1:  s = P[j, j] + var_y[j];  delta = y[t, n, j] - m[j];  g = P[:, j] / s
+#                                              m += g delta;  P -= s g g^T;  loglik[n] -= (log(2 pi s) + delta^2 / s) / 2
+#         means[t] = m;  covs[t] = P
+#
+# gp_ekf_eval's recursion with the linearisation at the mean replaced by the exact moments of the GP under the belief: the
+# two differ by tens of percent once the belief is as wide as a lengthscale.  One launch for all steps (cbfssm_gp_adf_f64),
+# alpha and the W_d tiles formed once per call, instead of a loop of transition_moments (one prepare, two pre-kernels, one
+# launch and about ten tensor-library ops per step) plus a dozen batched tensor-library ops for the update.  gp_ads_eval
+# chains the gain and sweep launches of gp_eks_eval behind it (cbfssm_gp_ads_f64): with cross[t] = P + Cx = Cov(h_t, h_{t-1})
+# the gain cross[t]^T (P-_t)^-1 is the ADF smoother gain.
+
+AdfResult = collections.namedtuple('AdfResult', 'means covs loglik pmeans pcovs cross info')
+
+
+def _adf_inputs(who, pack, m0, P0, a, y, var_x, var_y, cond):
+    """the argument checks of gp_ekf_eval: (m0, P0, a, y, var_x, var_y, cond, T, N, Dy) as contiguous float64 or None"""
+    dev = pack.buf.device
+    Do, Da = pack.Do, pack.D - pack.Do
+    if Da < 0:
+        raise ValueError('%s: the GP input dimension %d is smaller than its output dimension %d' % (who, pack.D, pack.Do))
+    f64 = lambda t: torch.as_tensor(t, dtype=torch.float64, device=dev).detach().contiguous()
+    y, m0, var_y = f64(y), f64(m0), f64(var_y)
+    assert y.dim() == 3 and m0.dim() == 2 and m0.shape == (y.shape[1], Do), 'y (T, N, Dy), m0 (N, Do)'
+    T, N, Dy = y.shape
+    if not 1 <= Dy <= Do:
+        raise ValueError('%s: y observes the first Dy state dimensions, 1 <= Dy <= %d (got %d)' % (who, Do, Dy))
+    assert tuple(var_y.shape) == (Dy,), 'var_y (Dy)'
+    if P0 is not None:
+        P0 = f64(P0)
+        assert tuple(P0.shape) == (N, Do, Do), 'P0 (N, Do, Do)'
+    if Da == 0:
+        assert a is None or tuple(a.shape) == (T, N, 0), 'a: None or (T, N, 0) when the GP takes the state alone'
+        a = None
+    else:
+        a = f64(a)
+        assert tuple(a.shape) == (T, N, Da), 'a (T, N, D - Do)'
+    if var_x is not None:
+        var_x = f64(var_x)
+        assert tuple(var_x.shape) == (Do,), 'var_x (Do)'
+    if cond is not None:
+        cond = torch.as_tensor(cond, device=dev)
+        assert tuple(cond.shape) == (T, N), 'cond (T, N)'
+        cond = (cond != 0).to(torch.float64).contiguous()
+    return m0, P0, a, y, var_x, var_y, cond, T, N, Dy
+
+
+def _adf_work(lib, lay, dev):
+    nwork = int(lib.cbfssm_gp_adf_work_elems(C.byref(lay)))
+    if nwork < 1:
+        raise _l.CbfssmHipError('cbfssm_gp_adf_work_elems refused the layout')
+    return torch.empty(nwork, dtype=torch.float64, device=dev)
+
+
+def gp_adf_eval(pack, m0, P0, a, y, var_x, var_y, cond=None):
+    """AdfResult(means (T, N, Do), covs (T, N, Do, Do), loglik (N), pmeans (T, N, Do), pcovs (T, N, Do, Do) (the one-step
+    predictive moments, before conditioning), cross (T, N, Do, Do) with cross[t] = Cov(h_t, h_{t-1}), row = new state,
+    info (N) int64) on a pack that is already prepared; arguments as gp_ekf_eval.  info[n] = 0, or t + 1 of the first step
+    at which a factorisation of chain n met a pivot <= 0, not finite, or below the floor a positive semi-definite belief
+    keeps it above (1 for I + S~, 1/2 for I/2 + S~) -- P0 not positive semi-definite: from that step on the chain's results and its loglik are NaN, no other chain is affected.  Every covs[t, n] and pcovs[t, n] is bitwise
+    symmetric.  Evaluation only: no grad_fn, nothing is launched without a chain or a step (loglik and info are then zero);
+    reading info as int64 is a device-side cast, not a host synchronisation."""
+    lib = _l.load()
+    lay, dev = pack.layout, pack.buf.device
+    Do = pack.Do
+    with torch.no_grad():
+        m0, P0, a, y, var_x, var_y, cond, T, N, Dy = _adf_inputs('gp_adf', pack, m0, P0, a, y, var_x, var_y, cond)
+        new = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)
+        means, covs, pmeans, pcovs, cross = new(T, N, Do), new(T, N, Do, Do), new(T, N, Do), new(T, N, Do, Do), new(T, N, Do, Do)
+        if N == 0 or T == 0:
+            return AdfResult(means, covs, torch.zeros(N, dtype=torch.float64, device=dev), pmeans, pcovs, cross,
+                             torch.zeros(N, dtype=torch.int64, device=dev))
+        loglik, info = new(N), new(N)
+        work = _adf_work(lib, lay, dev)
+        _l.check(lib.cbfssm_gp_adf_f64(C.byref(lay), _ptr(pack.buf), _ptr(m0), _ptr(P0), _ptr(a), _ptr(y), _ptr(cond),
+                                       _ptr(var_x), _ptr(var_y), Dy, N, T, _ptr(means), _ptr(covs), _ptr(loglik), _ptr(pmeans),
+                                       _ptr(pcovs), _ptr(cross), _ptr(info), _ptr(work), _stream()), 'cbfssm_gp_adf_f64')
+    return AdfResult(means, covs, loglik, pmeans, pcovs, cross, info.to(torch.int64))
+
+
+def gp_ads_eval(pack, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):
+    """EksResult, fields as gp_eks_eval, of the Rauch-Tung-Striebel smoother behind gp_adf_eval: means, covs, loglik, pmeans
+    and pcovs are gp_adf_eval's, bitwise.  info[n] is the forward pass's where that is non-zero -- the chain's smoothed
+    results are then NaN throughout -- and otherwise the sweep's, as in gp_eks_eval.  Every scovs[t, n] and init_cov[n] is
+    bitwise symmetric.  Evaluation only: no grad_fn, no host synchronisation, nothing is launched without a chain or a
+    step (loglik and info are then zero)."""
+    lib = _l.load()
+    lay, dev = pack.layout, pack.buf.device
+    Do = pack.Do
+    with torch.no_grad():
+        m0, P0, a, y, var_x, var_y, cond, T, N, Dy = _adf_inputs('gp_ads', pack, m0, P0, a, y, var_x, var_y, cond)
+        new = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)
+        means, covs, pmeans, pcovs, cross = new(T, N, Do), new(T, N, Do, Do), new(T, N, Do), new(T, N, Do, Do), new(T, N, Do, Do)
+        smeans, scovs, sm_init, sP_init = new(T, N, Do), new(T, N, Do, Do), new(N, Do), new(N, Do, Do)
+        lag1 = new(T, N, Do, Do) if lag_one else None
+        if N == 0 or T == 0:
+            return EksResult(smeans, scovs, torch.zeros(N, dtype=torch.float64, device=dev), means, covs, pmeans, pcovs, sm_init,
+                             sP_init, lag1, torch.zeros(N, dtype=torch.int64, device=dev))
+        loglik, info = new(N), new(N)
+        work = _adf_work(lib, lay, dev)
+        _l.check(lib.cbfssm_gp_ads_f64(C.byref(lay), _ptr(pack.buf), _ptr(m0), _ptr(P0), _ptr(a), _ptr(y), _ptr(cond),
+                                       _ptr(var_x), _ptr(var_y), Dy, N, T, _ptr(means), _ptr(covs), _ptr(loglik), _ptr(pmeans),
+                                       _ptr(pcovs), _ptr(cross), _ptr(smeans), _ptr(scovs), _ptr(sm_init), _ptr(sP_init),
+                                       _ptr(lag1), _ptr(info), _ptr(work), _stream()), 'cbfssm_gp_ads_f64')
     return EksResult(smeans, scovs, loglik, means, covs, pmeans, pcovs, sm_init, sP_init, lag1, info.to(torch.int64))
 
 

@@ -48,6 +48,12 @@ assumed-density filter), right where the belief is as wide as a lengthscale and 
 the (N, M, M) matrix of expected kernel products never reaches memory.  `GPModel.transition_moments(h, P, a)` is the
 Gaussian one-step prediction of the recurrence on top of it: m+, P+ and Cov(h, h+).  Both are evaluation only and for the
 diagonal q(z).
+
+`GPModel.adf(m0, P0, a, y, var_x, var_y, cond)` is the recursion that primitive was written for: the assumed-density
+(moment-matching) Kalman filter, `ekf` with the exact moments in place of the linearisation at the mean, as one launch for
+all steps -- the moment-match work of a step inside the time loop, alpha and the W_d tiles formed once per call.
+`GPModel.ads(...)` is the Rauch-Tung-Striebel smoother behind it (`eks`'s sweep on Cov(h_t, h_{t-1}) = P + Cx).  Both are
+evaluation only and for the diagonal q(z).
 """
 import ctypes as C
 import numpy as np
@@ -215,8 +221,8 @@ class GPModel:
     branch of gp_tf.py:150-159).  The third leaf is then `zeta_sqrt` (Do, M, M), unconstrained, initialised to
     sqrt(zeta_var) I; only its lower triangle is read and its gradient above the diagonal is exactly zero.  `zeta_std`
     returns the factors L_d, `zeta_var` the marginal variances diag(L_d L_d^T) as (M, Do).  `rollout`, `filter`,
-    `linearize`, `transition_jacobians`, `ekf`, `eks`, `moment_match` and `transition_moments` raise ValueError on such a
-    model."""
+    `linearize`, `transition_jacobians`, `ekf`, `eks`, `moment_match`, `transition_moments`, `adf` and `ads` raise ValueError
+    on such a model."""
 
     def __init__(self, in_dim, out_dim, num_points, gp_var, gp_len, zeta_mean, zeta_pos, zeta_var, dtype='float64',
                  device=None, seed=None, q_full=False):
@@ -518,3 +524,61 @@ class GPModel:
         low = torch.tril(P + Cm + Cm.transpose(1, 2) + fcov)
         Pn = low + torch.tril(low, -1).transpose(1, 2)
         return h + fmean, Pn, P + Cm, info
+
+    def adf(self, m0, P0, a, y, var_x, var_y, cond=None):
+        """The assumed-density (moment-matching) Kalman filter over this GP -- GP-ADF, PILCO's propagation: `ekf`'s
+        recursion with the linearisation at the mean replaced by the exact moments of `moment_match` under the belief,
+        which is what a belief as wide as a lengthscale needs.  One launch for all steps, per chain n:
+
+            for t in 0..T-1:
+                x = concat(m, a[t]);  S = blockdiag(P, 0)                     (the auxiliary input is known)
+                fmean, fcov, xcov = moment_match(x, S);  Cx = xcov[:, :out_dim]          (Cx[d, i] = Cov(f_d, h_i))
+                m- = m + fmean
+                cross[t] = P + Cx                          (= Cov(h_t, h_{t-1}), row = new state: the layout `eks` uses)
+                P- = P + Cx + Cx^T + fcov + diag(var_x)
+                pmeans[t], pcovs[t] = m-, P-
+                where cond[t, n], for j in 0..Dy-1:  s = P-[j, j] + var_y[j];  delta = y[t, n, j] - m-[j];  g = P-[:, j] / s
+                                                     m- += g delta;  P- -= s g g^T
+                                                     loglik[n] -= (log(2 pi s) + delta^2 / s) / 2
+                means[t], covs[t] = m, P = m-, P-
+
+        Arguments, shapes, the None conventions and the checks are `ekf`'s: m0 (N, out_dim), P0 (N, out_dim, out_dim) or
+        None (zero; only the lower triangle is read), a (T, N, in_dim - out_dim) or None, y (T, N, Dy) with
+        1 <= Dy <= out_dim, var_x (out_dim) or None, var_y (Dy), cond (T, N) of 0 / 1 or None (condition everywhere).  The
+        branch on cond is a select: y may hold NaN where cond = 0, it reaches no result; cond = 0 everywhere is exact-moment
+        uncertainty propagation with loglik exactly 0.  Returns the namedtuple AdfResult(means (T, N, out_dim), covs
+        (T, N, out_dim, out_dim), loglik (N), pmeans, pcovs, cross (T, N, out_dim, out_dim), info (N) int64).  Every
+        covs[t, n] and pcovs[t, n] is bitwise symmetric.  info[n] is 0, or t + 1 for the first step at which a
+        factorisation of chain n met a non-positive or non-finite pivot, or one below the floor that a positive
+        semi-definite belief keeps it above (1 for I + S~, 1/2 for I/2 + S~: this flags a negative definite P0 whose two
+        factors exist) -- possible only when P0 is not positive semi-definite: from that step on that chain's results and its loglik are NaN, and no other chain is affected.
+        Two calls give bitwise-identical results, and a chain's results do not depend on the other chains of the call.  No
+        host synchronisation; nothing is launched without a chain or a step.  Evaluation only, float64, diagonal q(z),
+        forward in time: the results carry no grad_fn whatever the leaves or the inputs ask for.  Raises ValueError on a
+        q_full=True model and when in_dim < out_dim."""
+        self._no_full_q('adf')
+        from ..hip import autograd as _ag
+        y = _f64(y, self.zeta_pos.device)
+        pack = self._prepared() if y.shape[0] * y.shape[1] else self._pack       # (nothing runs without a chain or a step)
+        return _ag.gp_adf_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond)
+
+    def ads(self, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):
+        """The Rauch-Tung-Striebel smoother behind `adf`.  The forward pass is `adf` itself (arguments and checks are its
+        own; means, covs, loglik, pmeans, pcovs are its results, bitwise); the backward sweep is `eks`'s, on
+        cross[t] = P + Cx:
+
+            (smeans, scovs)[T-1] = (means, covs)[T-1]
+            for t in T-1..0:   G = cross[t]^T (P-_t)^-1                                   (the ADF smoother gain)
+                               smeans[t-1] = means[t-1] + G (smeans[t] - pmeans[t])
+                               scovs[t-1]  = covs[t-1] + G (scovs[t] - pcovs[t]) G^T
+                               lag_one[t]  = G scovs[t] = Cov(h_{t-1}, h_t | y)
+
+        where time -1 is the initial belief (m0, P0).  Returns the namedtuple EksResult, fields as in `eks`; scovs and
+        init_cov are bitwise symmetric.  info[n] is `adf`'s where that is non-zero -- that chain's smoothed results are then
+        NaN throughout -- and otherwise the sweep's, as in `eks`.  No host synchronisation; nothing is launched without a
+        chain or a step.  Evaluation only.  Raises ValueError on a q_full=True model and when in_dim < out_dim."""
+        self._no_full_q('ads')
+        from ..hip import autograd as _ag
+        y = _f64(y, self.zeta_pos.device)
+        pack = self._prepared() if y.shape[0] * y.shape[1] else self._pack       # (nothing runs without a chain or a step)
+        return _ag.gp_ads_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond, lag_one=lag_one)

@@ -1,0 +1,2 @@
+#include "cbfssm_gp_adf.hpp"
+CBF_GPADF_INSTANTIATE(16)

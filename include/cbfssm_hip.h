@@ -297,6 +297,43 @@ int cbfssm_gp_moment_match_f64(const cbfssm_pack_layout* layout, const double* p
                                int64_t npts, double* fmean, double* fcov, double* xcov, double* info, double* work, void* stream);
 
 /*
+ * Assumed-density (moment-matching) Kalman filter over the transition of one sparse GP, and the Rauch-Tung-Striebel
+ * smoother behind it: the recursion of cbfssm_gp_ekf_f64 with the exact moments of cbfssm_gp_moment_match_f64 in place of
+ * the linearisation at the mean (GP-ADF).  Per chain n and step t, with x = concat(m, a[t]) and S = blockdiag(P, 0):
+ *
+ *   fmean, fcov, xcov = moment_match(x, S);  Cx = xcov[:, :Do]
+ *   m- = m + fmean;  cross[t] = P + Cx;  P- = P + Cx + Cx^T + fcov + diag(var_x);  pmeans[t], pcovs[t] = m-, P-
+ *   where cond[t][n] != 0: the Dy scalar updates of cbfssm_gp_ekf_f64;  means[t], covs[t] = m, P = m-, P-
+ *
+ * cbfssm_gp_adf_f64: the inputs of cbfssm_gp_ekf_f64 -> means, covs, loglik, pmeans (T, N, Do), pcovs, cross (T, N, Do, Do)
+ *   and info (N) doubles.  info[n] = 0, or t + 1 of the first step at which a factorisation of chain n met a pivot <= 0,
+ *   not finite, or below what a positive semi-definite belief can give (1 for I + S~, 1/2 for I/2 + S~, less rounding) --
+ *   P0 not positive semi-definite: from that step on the chain's results and its loglik are NaN, no other
+ *   chain is affected.  Every covs[t][n] and pcovs[t][n] is bitwise symmetric; only the lower triangle of P0 is read; a y
+ *   entry at cond = 0 is chosen away by a select.  Three launches on one stream: alpha = K^-1 mu and the W_d tiles once per
+ *   call in `work` (cbfssm_gp_adf_work_elems doubles: 16 * 16 * NBLK + Do * NBLK^2 * 256), then ONE launch for all steps,
+ *   one workgroup per 16 chains.  No atomics, no allocation, no host synchronisation, two calls are bitwise identical, a
+ *   chain's results do not depend on the other chains of the call; nothing is launched at N = 0 or T = 0.
+ * cbfssm_gp_ads_f64: the same forward pass (its seven results bitwise), then the gain and sweep launches of
+ *   cbfssm_gp_eks_f64 on cross[t] = P + Cx -> smeans, scovs, sm_init, sP_init, lag1 (or NULL) as there.  info: the forward
+ *   pass's where that is non-zero (the chain's smoothed results are then NaN throughout), else the sweep's.  cross is
+ *   workspace here: once the gains are formed its first N entries carry the sweep's info to the kernel that merges the two.
+ *
+ * Limits and refusals as cbfssm_gp_ekf_f64, the limits first, before any pointer is looked at: -3; NULL layout, pack, m0, y,
+ * var_y, work or any output but lag1, NULL a with D > Do, or N, T, Dy < 0: -1.  The count returns -1 for a bad layout.
+ */
+int64_t cbfssm_gp_adf_work_elems(const cbfssm_pack_layout* layout);      /* gp_tf.py:132-161, cbfssm.py:199-221,245-251 */
+int cbfssm_gp_adf_f64(const cbfssm_pack_layout* layout, const double* pack, const double* m0, const double* P0,
+                      const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                      int Dy, int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans,
+                      double* pcovs, double* cross, double* info, double* work, void* stream);
+int cbfssm_gp_ads_f64(const cbfssm_pack_layout* layout, const double* pack, const double* m0, const double* P0,
+                      const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                      int Dy, int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans,
+                      double* pcovs, double* cross, double* smeans, double* scovs, double* sm_init, double* sP_init,
+                      double* lag1, double* info, double* work, void* stream);
+
+/*
  * ---- extended Kalman filter over the transition of ONE sparse GP: a Gaussian belief (m, P) per chain, carried through
  * time by the local linear model above inside the recurrence of CBF-SSM (cbfssm/model/cbfssm.py:199-221) and conditioned
  * on observations of the first Dy state dimensions (cbfssm.py:245-251), y = x[:Dy] + N(0, diag(var_y)).  Forward in time,
