@@ -27,7 +27,10 @@ and three more tables exercise the host-side schedules of the full-q path (cbfss
 Measured on the CPU (reference against second coding): the filter codings agree to 6.1e-13 of max |traj|, 4.0e-14 on kl and
 3.0e-11 of the largest entry of every gradient tensor; no filter gradient tensor's largest entry is below 5.1e-2 and no kl
 below 35.4; the mask's zero fraction lies in 0.25 .. 0.42.  The full-q codings agree to 6.0e-13 (values) and 2.2e-11
-(gradients) on the rows, to 4.2e-12 at worst on the long and slice cases; min fvar is 3.7e-2.  At M = 1, K is a scalar and
+(gradients) on the rows, to 1.5e-11 at worst on the long and slice cases (the five long cases per table added for the other
+tile heights: 1.5e-11 at (320, 12, 4, 16449), 1.3e-12 or better elsewhere; their cond_2(K_mm + 1e-8 I) is at most 1.6e4,
+asserted to stay below 1e5; of the older long rows (300, 6, 4) has 1.6e5); min fvar is 3.7e-2 on the rows and 2.6e-2 on the
+long cases.  At M = 1, K is a scalar and
 the gradient of prior_kl alone with respect to zeta_pos and lengthscales_unc is exactly zero: KL_ZERO names those two.
 
 To extend: a new tile height, input width or trim in any of the four launcher families makes
@@ -45,8 +48,11 @@ K_FACTORS = (1.0, 1.3, 2.0)
 
 # (M, D, Do, npts): 260 and 257 column blocks on the 256 workgroups of the stash heights, 1026 on the 1024 of NBLK <= 2
 FULLQ_BWD_LONG = LONG_ROWS
-# 4099 / 1027 / 2051 column blocks on the forward's 4096 (NBLK <= 2) / 1024 (stash heights) / 2048 (NBLK <= 7) workgroups
-FULLQ_FWD_LONG = [(12, 4, 3, 65573), (130, 6, 4, 16421), (50, 9, 2, 32805)]
+# 4099 / 1027 / 2051 column blocks on the forward's 4096 (NBLK <= 2) / 1024 (stash heights) / 2048 (NBLK <= 7) workgroups;
+# then the other five tile heights, npts = 16 (cap + k) + r with cap = fullq_fwd_cap(NBLK), 1 <= k <= 4, 1 <= r <= 15
+FULLQ_FWD_LONG = [(12, 4, 3, 65573), (130, 6, 4, 16421), (50, 9, 2, 32805),
+                  (24, 8, 8, 16 * (4096 + 1) + 7), (99, 7, 5, 16 * (2048 + 3) + 9), (180, 6, 2, 16 * (1024 + 1) + 3),
+                  (250, 12, 6, 16 * (1024 + 3) + 13), (320, 12, 4, 16 * (1024 + 4) + 1)]
 # 18 column blocks: 2 slices of 9 + 9 (the last block ragged); 41: 3 slices of 14 + 14 + 13
 FULLQ_SLICE_ROWS = [(50, 9, 2, 277), (24, 8, 8, 643)]
 

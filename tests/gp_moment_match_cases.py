@@ -19,6 +19,8 @@ The covariance of point n is one of three kinds, in turn (KINDS[n % 3]):
 Measured here over every rank2 belief of the GPU tests (tests/test_gp_moment_match_cpu.py, per case tensor): (a) and (b) agree
 to 7.2e-13 (fmean), 5.6e-11 (fcov) and 3.5e-13 (xcov) of the largest entry, and to 1.5e-10 on the strictly lower triangle of fcov
 relative to its own largest entry, which is never below 7.6e-3 on the rows of gp_tile_grid.ROWS; cond_2(K) is at most 9.8e4.
+LONG_CASES (the shapes of gp_linearize_cases.LONG_CASES) stay inside these figures: cond_2 at most 1.9e3, and at worst
+2.2e-14 / 9.5e-13 / 1.7e-14 / 5.8e-12, all at (320, 12, 4).
 Results are cached per case: treat them as read-only."""
 import functools
 
@@ -40,6 +42,11 @@ EDGE_CASES = [(1, 1, 1, 1), (40, 15, 3, 17), (40, 16, 3, 17), (112, 24, 16, 17),
 # npts = 37 repeated with period 37 (coprime to the 16 points of a group): a wrong point index still shows, and (b) has 13
 # quadratures to do instead of 5474
 LONG_CASE = (12, 4, 3, 16 * 1026 + 5)
+# and at every tile height (the slot and region aliasing of cbfssm_gp_mm.hpp differs per height): npts = 16 (cap + k) + r,
+# cap = GpBwdCfg<NBLK>::MAXWG, 1 <= k <= 4, 1 <= r <= 15; the same period-37 beliefs (distinct_points)
+LONG_CASES = [LONG_CASE, (24, 8, 8, 16 * (1024 + 2) + 11), (50, 9, 2, 16 * (512 + 1) + 13), (99, 7, 5, 16 * (512 + 4) + 3),
+              (160, 9, 3, 16 * (256 + 3) + 7), (180, 12, 3, 16 * (256 + 1) + 15), (250, 12, 6, 16 * (256 + 2) + 1),
+              (320, 12, 4, 16 * (256 + 4) + 9)]
 # Voliro's recognition shape: state 6, inputs (u, y) 13
 VOLIRO_CASE = (20, 19, 6, 37)
 # transition_moments: a stash height, Voliro, and a GP that takes the state alone (D = Do, a = None)

@@ -23,11 +23,13 @@ A row is (name, M, D, Do); its inputs are derived, not tabulated:
     predict_case(row)  (M, D, Do, npts = 37) of tests/gp_autograd_cases.py: three column blocks, the last ragged
 
 LONG_ROWS (M, D, Do, npts) make the persistent column-block loop of gp_predict_bwd_kernel go round a second time: more
-column blocks than the workgroup cap of the height (GpBwdCfg::MAXWG), at most twice as many.
+column blocks than the workgroup cap of the height (GpBwdCfg::MAXWG), at most twice as many -- one row per tile height,
+because the wave layout, and with it what a second trip can find left over in LDS, differs per height.
 
 Measured on the CPU over the 36 rows (oracle against second coding, see evaluate_predict): cond_2(K_mm + 1e-8 I) is at
 most 9.8e4; the two codings agree on every gradient tensor to 2.7e-11 of its largest entry (rollout) and 1.3e-11
-(predict; 5.5e-11 on the long rows), on the trajectories to 3.1e-12 of max |traj| and on the entropy to 5e-14 relative;
+(predict; 5.5e-11 on the first three long rows; on the five added for the other tile heights cond_2 is at most 1.6e4 and
+the codings agree to 5.4e-13), on the trajectories to 3.1e-12 of max |traj| and on the entropy to 5e-14 relative;
 no gradient tensor's largest entry is below 7.9e-3.  D = 4 is not used at M >= 113: on this input family (256, 4, 2) has
 cond 4e6 and the codings then agree on the trajectory to 2.9e-9 only.
 
@@ -70,8 +72,24 @@ ROWS = [
 ROW_IDS = [r[0] for r in ROWS]
 ROW_BY_NAME = {r[0]: r for r in ROWS}
 
-# (M, D, Do, npts): 260 and 257 column blocks on the 256 workgroups of the stash heights, 1026 on the 1024 of NBLK <= 2
-LONG_ROWS = [(130, 6, 4, 4149), (300, 6, 4, 4101), (12, 4, 3, 16405)]
+# (M, D, Do, npts): 260 and 257 column blocks on the 256 workgroups of the stash heights, 1026 on the 1024 of NBLK <= 2;
+# then one row for each of the other five tile heights, npts = 16 (cap + k) + r with cap = max_workgroups(NBLK), 1 <= k <= 4,
+# 1 <= r <= 15 (LONG_K_R): a few workgroups go round a second time and the last column block is ragged.  Their (M, D, Do)
+# are those of rows of ROWS (nb2_mid_dk2, nb4_mid_dk4, nb7_kt3_dk6 -- the C3 shape --, nb13_mid_dk2, nb16_mid_dk4)
+LONG_ROWS = [(130, 6, 4, 4149), (300, 6, 4, 4101), (12, 4, 3, 16405),
+             (24, 8, 8, 16 * (1024 + 1) + 7), (50, 9, 2, 16 * (512 + 2) + 3), (100, 21, 14, 16 * (512 + 3) + 9),
+             (180, 6, 2, 16 * (256 + 2) + 11), (250, 12, 6, 16 * (256 + 4) + 13)]
+
+
+def long_k_r(npts, cap):
+    """(k, r) of npts = 16 (cap + k) + r with 1 <= r <= 16"""
+    blocks = (npts + 15) // 16
+    return blocks - 1 - cap, npts - 16 * (blocks - 1)
+
+
+def long_heights(rows):
+    """the tile heights of a long table"""
+    return sorted(leaf_key(M, D, Do)[0] for M, D, Do, _ in rows)
 
 # chains 0..15 of a row's N = 21 run against an N = 16 run: one stash height, one below
 CHAIN_GROUP_ROWS = ['nb13_mid_dk2', 'nb7_kt1_dk4']

@@ -11,7 +11,8 @@ by two kernels on the same device.  The filtered results are compared with GPMod
 Measured on an MI355X (profiles/gp_eks/README.md), worst of the seven tensors: over the 36 grid rows 6.7e-12 in the
 automatic and the dense form and 1.3e-11 in the two-triangular form (scovs, pcovs), all at (257, 6, 3); 2.3e-11 (smeans) after
 forty steps, where the two CPU references differ by 2.0e-11; at most 3.9e-13 on the other mask and edge cases; the
-cross-checks 3.3e-16 (pcovs[0]), 2.0e-15 (pmeans[0]) and 1.5e-16 (cross[0]).  The file takes about 3.6 seconds."""
+cross-checks 3.3e-16 (pcovs[0]), 2.0e-15 (pmeans[0]) and 1.5e-16 (cross[0]).  The file takes about 3.6 seconds without the two
+tests over 65 541 steps at its end, whose times profiles/gp_surface_poison/README.md gives."""
 import ctypes as C
 
 import numpy as np
@@ -256,6 +257,100 @@ def test_a_failed_factorisation_is_reported_and_turns_one_chain_into_nan():
     for k in ('loglik', 'init_mean', 'init_cov'):
         assert torch.equal(getattr(good, k)[others], getattr(bad, k)[others]), k
     _check(c, good, 'good')
+
+
+# ---- more steps than the gain kernel's grid has rows: its loop `for t = blockIdx.y; t < T; t += gridDim.y` goes round
+LONG_HORIZON = ec.case(12, 4, 3, N=5, T=65535 + 6, Dy=3, mask='ones')
+
+
+def _solve_spd(P, B):
+    """P^-1 B for symmetric positive definite P (..., d, d) by elimination without pivoting, in the dtype of the arguments
+    (np.linalg does not take np.longdouble)"""
+    P, B = P.copy(), B.copy()
+    d = P.shape[-1]
+    for k in range(d):
+        for i in range(k + 1, d):
+            f = P[..., i, k] / P[..., k, k]
+            P[..., i, :] -= f[..., None] * P[..., k, :]
+            B[..., i, :] -= f[..., None] * B[..., k, :]
+    X = np.empty_like(B)
+    for k in range(d - 1, -1, -1):
+        acc = B[..., k, :].copy()
+        for j in range(k + 1, d):
+            acc -= P[..., k, j, None] * X[..., j, :]
+        X[..., k, :] = acc / P[..., k, k, None]
+    return X
+
+
+def rts_numpy(means, covs, pmeans, pcovs, cross, m0, P0, dtype=np.float64):
+    """the formulas of gp_eks_cases.reference_rts over filtered results (T, N, ...), vectorised over the chains: the gains
+    G_t = (cross_t)^T (P-_t)^-1 of all steps at once (they depend on the filter alone), then the backward sweep"""
+    means, covs, pmeans, pcovs, cross, m0, P0 = [np.asarray(v, dtype=dtype) for v in (means, covs, pmeans, pcovs, cross, m0, P0)]
+    T = means.shape[0]
+    G = np.swapaxes(_solve_spd(pcovs, cross), -1, -2)                          # P- symmetric: (P-^-1 cross)^T
+    GT = np.swapaxes(G, -1, -2)
+    smeans, scovs, lag1 = np.empty_like(means), np.empty_like(covs), np.empty_like(covs)
+    ms, Ps = means[T - 1], covs[T - 1]
+    smeans[T - 1], scovs[T - 1] = ms, Ps
+    for t in range(T - 1, -1, -1):
+        mf, Pf = (means[t - 1], covs[t - 1]) if t > 0 else (m0, P0)
+        lag1[t] = G[t] @ Ps
+        ms = mf + (G[t] @ (ms - pmeans[t])[:, :, None])[:, :, 0]
+        Ps = Pf + G[t] @ (Ps - pcovs[t]) @ GT[t]
+        if t > 0:
+            smeans[t - 1], scovs[t - 1] = ms, Ps
+    return {'smeans': smeans, 'scovs': scovs, 'init_mean': ms, 'init_cov': Ps, 'lag_one': lag1}
+
+
+def test_more_steps_than_the_gain_kernel_has_grid_rows():
+    """T = 65535 + 6 steps, N = 5 chains (one sweep wave and a ragged one), the smallest tile, every step fully observed
+    (Dy = Do = 3, cond NULL) so that the belief stays bounded, lag_one on: the step loop of gp_eks_gain_kernel goes round a
+    second time for the first six steps.  The forward filter is pinned elsewhere; here the gain and sweep kernels are held to
+    the numpy Rauch-Tung-Striebel recursion over the filtered results of the SAME call (means, covs, pmeans, pcovs, cross of
+    the raw entry point), by the file's 1e-8 rule.  That recursion in np.longdouble against float64, on these inputs,
+    measured on an MI355X's results: smeans 1.5e-16, scovs 3.8e-16, init_mean 2.5e-16, init_cov 9.6e-16, lag_one
+    4.1e-16 of the largest entry -- seven orders inside the rule (the sweep contracts: every step is observed, so rounding
+    does not accumulate over the 65541 steps; max |cov| is 0.105, max |mean| 2.7).  The kernels against the float64
+    recursion: 2.3e-16, 7.0e-16, 3.6e-16, 1.0e-15, 6.4e-16.  The call is 1.9 s of kernel time (29 us per step of a serial
+    loop); the output buffers of the raw call start as NaN, so a step whose gain was never formed shows."""
+    c = LONG_HORIZON
+    M, D, Do, N, T, Dy = c[:6]
+    assert T > 65535 and N == 5 and Do <= 3 and Dy == Do and ec.make_inputs(c)['cond'] is None
+    assert grid.leaf_key(M, D, Do)[0] == min(grid.dispatch_heights())
+    rc, b = _raw(c)
+    assert rc == 0
+    assert all(bool(torch.isfinite(v).all()) for v in b.values())
+    assert torch.equal(b['info'], torch.zeros_like(b['info']))
+    (m0, P0, *_), _ = _args(c)
+    host = {k: v.cpu().numpy() for k, v in b.items()}
+    ref = rts_numpy(host['means'], host['covs'], host['pmeans'], host['pcovs'], host['cross'], m0.cpu().numpy(),
+                    _sym(P0).cpu().numpy())
+    errs = {k: sc.rel_err(host[k], ref[k]) for k in ref}
+    print('long horizon: ' + '  '.join('%s %.2e' % kv for kv in errs.items()))
+    assert all(e < RULE for e in errs.values()), errs
+    assert torch.equal(b['smeans'][T - 1], b['means'][T - 1]) and torch.equal(b['scovs'][T - 1], b['covs'][T - 1])
+
+
+def test_ads_over_more_steps_than_the_gain_kernel_has_grid_rows():
+    """the same inputs through GPModel.ads, which runs the same gain and sweep kernels behind the moment-matching filter:
+    results of the shapes of eks, finite, info zero.  The call runs with every allocation of the glue filled with NaN
+    (tests/gp_surface_poison.py): the gain of a step the loop left out would stay NaN in its slot and reach the smoothed
+    results of every earlier step.  Moment matching inside each of the 65541 steps makes this the longer of the two calls."""
+    import gp_surface_poison as gsp
+    c = LONG_HORIZON
+    M, D, Do, N, T, Dy = c[:6]
+    args, cond = _args(c)
+    gp = _gp(c)
+    with gsp.poisoned_allocations(gsp.WORDS['nan']):
+        res = gp.ads(*args, cond=cond, lag_one=True)
+    assert torch.equal(res.info, torch.zeros(N, dtype=torch.int64, device=DEV))
+    vec, mat = (T, N, Do), (T, N, Do, Do)
+    shapes = {'smeans': vec, 'scovs': mat, 'means': vec, 'covs': mat, 'pmeans': vec, 'pcovs': mat, 'lag_one': mat,
+              'init_mean': (N, Do), 'init_cov': (N, Do, Do), 'loglik': (N,)}
+    for k, shape in shapes.items():
+        v = getattr(res, k)
+        assert tuple(v.shape) == shape and bool(torch.isfinite(v).all()), k
+    assert torch.equal(res.smeans[T - 1], res.means[T - 1]) and torch.equal(res.scovs[T - 1], res.covs[T - 1])
 
 
 def test_python_surface():

@@ -76,8 +76,10 @@ def test_derived_cases():
     cases = [fg.filter_case(r) for r in fg.ROWS]
     assert {c[5] for c in cases} == {True, False} and {c[6] for c in cases} == {True, False}
     assert {c[7] for c in cases} == {1.0, 1.3, 2.0}
-    assert fg.FULLQ_BWD_LONG == [(130, 6, 4, 4149), (300, 6, 4, 4101), (12, 4, 3, 16405)]
-    assert fg.FULLQ_FWD_LONG == [(12, 4, 3, 65573), (130, 6, 4, 16421), (50, 9, 2, 32805)]
+    assert fg.FULLQ_BWD_LONG == [(130, 6, 4, 4149), (300, 6, 4, 4101), (12, 4, 3, 16405), (24, 8, 8, 16407), (50, 9, 2, 8227),
+                                 (100, 21, 14, 8249), (180, 6, 2, 4139), (250, 12, 6, 4173)]
+    assert fg.FULLQ_FWD_LONG == [(12, 4, 3, 65573), (130, 6, 4, 16421), (50, 9, 2, 32805), (24, 8, 8, 65559),
+                                 (99, 7, 5, 32825), (180, 6, 2, 16403), (250, 12, 6, 16445), (320, 12, 4, 16449)]
     assert fg.FULLQ_SLICE_ROWS == [(50, 9, 2, 277), (24, 8, 8, 643)]
 
 
@@ -123,7 +125,19 @@ def test_long_rows_go_round_the_persistent_loops_twice():
             caps.add((gg.max_workgroups(nb), nb > 7))
         assert sum(stash for _, stash in caps) >= 1, 'a stash height among each long set'
         assert {c for c, _ in caps} >= {1024, 256}
+        # one long case at every tile height; the rows after the first three by the rule npts = 16 (cap + k) + r
+        assert gg.long_heights(rows) == sorted(HEIGHTS)
+        for M, D, Do, npts in rows[3:]:
+            k, r = gg.long_k_r(npts, cap_of(fg.leaf_key(M, D, Do)[0]))
+            assert 1 <= k <= 4 and 1 <= r <= 15, (M, npts, k, r)
+            assert M < 113 or D >= 6, (M, D)
+            cond = gg.kmm_condition(M, D, Do)
+            print('%s cond_2(K_mm + jitter I) %.3e' % ((M, D, Do, npts), cond))
+            assert cond <= 1e5, (M, D, Do, cond)               # (the bound the rows of gp_tile_grid.ROWS keep)
+        # the three rows each table had before: 2.5e3, 59 and, at (300, 6, 4) of FULLQ_BWD_LONG alone, 1.6e5 (below 1e6)
+        assert all(gg.kmm_condition(*r[:3]) < 1e6 for r in rows[:3])
     assert {fg.fullq_fwd_cap(fg.leaf_key(*r[:3])[0]) for r in fg.FULLQ_FWD_LONG} == {4096, 1024, 2048}
+    assert {fg.fullq_bwd_cap(fg.leaf_key(*r[:3])[0]) for r in fg.FULLQ_BWD_LONG} == {1024, 512, 256}
     # no other full-q case of the suite exceeds the forward cap, and the only one above the backward cap is at NBLK 7
     for M, D, Do, npts in fq.CASES:
         nb = fg.leaf_key(M, D, Do)[0]

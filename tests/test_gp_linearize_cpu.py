@@ -29,6 +29,33 @@ def test_autodiff_and_closed_form_agree_ill_conditioned(case):
     assert em < 1e-7 and ev < 1e-7
 
 
+@pytest.mark.parametrize('case', lc.LONG_CASES, ids=str)
+def test_autodiff_and_closed_form_agree_on_the_long_cases(case):
+    """cond_2(K_mm + jitter I) <= 1e5, the bound of gp_tile_grid.ROWS (measured: at most 1.9e3), and the 1e-12 of the
+    well-conditioned cases (measured: 2.9e-14); fmean and fvar agree entry by entry 100 times inside the rtol 1e-8 / atol
+    1e-12 the GPU test holds them to (measured: 0.9 % of it)"""
+    a, b = lc.reference_autodiff(*case), lc.reference_closed_form(*case)
+    em, ev = lc.rel_err(b['dmean'], a['dmean']), lc.rel_err(b['dvar'], a['dvar'])
+    print('%s cond %.1e  dmean %.1e  dvar %.1e' % (case, b['cond'], em, ev))
+    assert b['cond'] <= 1e5
+    assert em < 1e-12 and ev < 1e-12
+    for k in ('fmean', 'fvar'):
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-10, atol=1e-14)
+
+
+def test_long_cases_go_round_the_column_block_loop_twice_at_every_tile_height():
+    import gp_tile_grid as grid
+    import tile_grid as tg
+    assert lc.LONG_CASES[0] == lc.LONG_CASE
+    assert grid.long_heights(lc.LONG_CASES) == sorted(grid.dispatch_heights())
+    host = tg._read('cbfssm_gp_lin.hip')
+    assert 'const int64_t cap = gp_lin_maxwg(L->NBLK);' in host and 'case NB: return GpBwdCfg<NB>::MAXWG;' in host
+    for M, D, Do, npts in lc.LONG_CASES:
+        k, r = grid.long_k_r(npts, grid.max_workgroups(grid.leaf_key(M, D, Do)[0]))
+        assert 1 <= k <= 4 and 1 <= r <= 15, (M, npts, k, r)
+        assert M < 113 or D >= 6, (M, D)
+
+
 def test_autodiff_against_central_differences():
     """(a) at (12, 4, 3, 5): h = 1e-5 on inputs of size 1 leaves a truncation error of h^2 |f'''| / 6 ~ 1e-10 and a rounding
     error of eps |f| / h ~ 1e-11; the bound is 1e-7 of the largest entry"""

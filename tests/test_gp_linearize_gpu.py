@@ -120,6 +120,21 @@ def test_grid_stride_more_column_blocks_than_workgroups():
     _check(case, _linearize(case), 'long')
 
 
+@pytest.mark.parametrize('case', lc.LONG_CASES[1:], ids=str)
+def test_grid_stride_second_trip_at_every_tile_height(case):
+    """a few workgroups take a second column block, the last one ragged; the points of the last two column blocks give
+    bitwise what a call on those points alone gives -- a second trip sees no state of the first"""
+    M, D, Do, npts = case
+    assert (npts + 15) // 16 > grid.max_workgroups(grid.leaf_key(M, D, Do)[0])
+    out = _linearize(case)
+    _check(case, out, 'long')
+    s = 16 * ((npts + 15) // 16 - 2)
+    p, X, _, _ = gc.make_inputs(*case)
+    tail = _model(p, M, D, Do).linearize(_dev(X[s:]))
+    for g, t in zip(out, tail):
+        assert torch.equal(g[s:], t)
+
+
 @pytest.mark.parametrize('M,D,Do', [(100, 21, 14), (200, 13, 7)])
 def test_batch_independence_and_repeatability(M, D, Do):
     p, X, _, _ = gc.make_inputs(M, D, Do, 41)

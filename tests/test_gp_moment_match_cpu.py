@@ -25,7 +25,7 @@ import tile_grid as tg
 
 # every case of the GPU file whose beliefs are 'mixed' (rank2 every third point), and the rank-one case
 MIXED_CASES = [(M, D, Do, mc.N_POINTS) for _, M, D, Do in grid.ROWS] + mc.EDGE_CASES + \
-              [mc.VOLIRO_CASE, mc.LONG_CASE, (113, 9, 1, 17), (300, 21, 7, 19), (30, 7, 5, 9)]
+              [mc.VOLIRO_CASE, mc.LONG_CASE, (113, 9, 1, 17), (300, 21, 7, 19), (30, 7, 5, 9)] + mc.LONG_CASES
 BOUND = 1e-9
 
 
@@ -49,6 +49,19 @@ def test_closed_form_against_quadrature(case):
     assert sorted(quad) == [n for n in range(mc.distinct_points(case[3])) if kinds[n] == 'rank2'] and quad
     _compare('%s cond %.1e' % (case, ref['cond']), ref, quad)
     assert ref['cond'] < 1e6
+    assert ref['cond'] <= 1e5 or case not in mc.LONG_CASES
+
+
+def test_long_cases_go_round_the_point_group_loop_twice_at_every_tile_height():
+    assert mc.LONG_CASES[0] == mc.LONG_CASE
+    assert grid.long_heights(mc.LONG_CASES) == sorted(grid.dispatch_heights())
+    assert 'const int64_t cap = gp_mm_maxwg(L->NBLK);' in tg._read('cbfssm_gp_mm.hip')
+    assert 'case NB: return GpBwdCfg<NB>::MAXWG;' in tg._read('cbfssm_gp_mm.hip')
+    for M, D, Do, npts in mc.LONG_CASES:
+        k, r = grid.long_k_r(npts, grid.max_workgroups(grid.leaf_key(M, D, Do)[0]))
+        assert 1 <= k <= 4 and 1 <= r <= 15, (M, npts, k, r)
+        assert M < 113 or D >= 6, (M, D)
+        assert mc.distinct_points(npts) == mc.N_POINTS           # the period-37 repetition of distinct beliefs
 
 
 def test_closed_form_against_quadrature_rank_one():

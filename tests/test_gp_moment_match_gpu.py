@@ -99,6 +99,21 @@ def test_grid_stride_more_point_groups_than_workgroups():
     _check('long', _run(case), mc.reference_closed_form(*case))
 
 
+@pytest.mark.parametrize('case', mc.LONG_CASES[1:], ids=str)
+def test_grid_stride_second_trip_at_every_tile_height(case):
+    """a few workgroups take a second point group, the last one ragged; the points of the last two groups give bitwise
+    what a call on those points alone gives -- a second trip sees no state of the first"""
+    M, D, Do, npts = case
+    assert (npts + 15) // 16 > grid.max_workgroups(grid.leaf_key(M, D, Do)[0])
+    out = _run(case)
+    _check('long %s' % (case,), out, mc.reference_closed_form(*case))
+    s = 16 * ((npts + 15) // 16 - 2)
+    p, mean, cov, _ = mc.make_beliefs(*case)
+    tail = _model(p, M, D, Do).moment_match(_dev(mean[s:]), _dev(cov[s:]))
+    for g, t in zip(out, tail):
+        assert torch.equal(g[s:], t)
+
+
 @pytest.mark.parametrize('case', [(100, 21, 14, 19), (200, 13, 7, 19)], ids=str)
 def test_zero_covariance_is_predict(case):
     """cov = 0 and cov = None: fmean and diag fcov are the GPU's own predict, the off-diagonal is that of (a), xcov is

@@ -90,6 +90,14 @@ def test_long_rows_go_round_the_persistent_loop_twice():
         caps.add((cap, nb > 7))
     assert {c for c, _ in caps} >= {1024, 256} and sum(stash for _, stash in caps) >= 1
     assert len([1 for M, _, _, _ in gg.LONG_ROWS if M > 112]) >= 2
+    # one long row at every tile height, all three caps; the rows after the first three by the rule npts = 16 (cap + k) + r
+    assert gg.long_heights(gg.LONG_ROWS) == sorted(gg.dispatch_heights())
+    assert {c for c, _ in caps} == {1024, 512, 256}
+    assert gg.LONG_ROWS[:3] == [(130, 6, 4, 4149), (300, 6, 4, 4101), (12, 4, 3, 16405)]
+    for M, D, Do, npts in gg.LONG_ROWS[3:]:
+        k, r = gg.long_k_r(npts, gg.max_workgroups(gg.leaf_key(M, D, Do)[0]))
+        assert 1 <= k <= 4 and 1 <= r <= 15, (M, npts, k, r)
+        assert M < 113 or D >= 6, (M, D)
 
 
 def test_chain_group_rows_are_one_stash_height_and_one_below():
@@ -142,6 +150,7 @@ def test_long_row_reference_alone_stays_inside_the_tolerances(case):
     cond = gg.kmm_condition(*case[:3])
     print('cond_2(K_mm + jitter I) %.3e' % cond)
     assert cond < 1e6, cond
+    assert cond <= 1e5 or case in gg.LONG_ROWS[:3], cond       # (the bound the rows of ROWS keep)
     pref, psec = gg.predict_reference(case), gg.evaluate_predict(case, 'second')
     for k in ('X',) + gc.PARAMS:
         _agree('predict: ' + k, psec['g_' + k], pref['g_' + k], 1e-8)
