@@ -6,26 +6,11 @@
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_adf.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPADF_DECLARE)
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
-
-// cbfssm_gp_lin.hip
-__global__ void gp_lin_alpha_kernel(const double* Kinv, const double* G, const double* muB, int M, int Do, int MP, int tri,
-                                    double* alpha);
-// cbfssm_gp_mm.hip
-__global__ void gp_mm_w_kernel(const double* Kinv, const double* s2B, int M, int NBLK, double* Wimg);
-// cbfssm_gp_ekf.hip
-bool gp_ekf_layout_ok(const cbfssm_pack_layout* L);
-int gp_ekf_check_sizes(const char* who, const cbfssm_pack_layout* L, int Dy, int64_t N, int64_t T);
-// cbfssm_gp_eks.hip
-int gp_eks_sweep_launch(const char* who, const double* m0, const double* P0, const double* means, const double* covs,
-                        const double* pmeans, const double* pcovs, const double* cross, double* smeans, double* scovs,
-                        double* sm_init, double* sP_init, double* lag1, double* info, int64_t N, int64_t T, int Do,
-                        hipStream_t st);
 
 static int dispatch_gp_adf(int NBLK, int DK, const GpAdfArgs& a, hipStream_t st)
 {
@@ -80,7 +65,7 @@ extern "C" {
 
 int64_t cbfssm_gp_adf_work_elems(const cbfssm_pack_layout* L)
 {
-    if (!gp_ekf_layout_ok(L)) return -1;                // moment_match's limits and D >= Do
+    if (!gp_layout_ok(L, GP_NEED_STATE)) return -1;                // moment_match's limits and D >= Do
     return int64_t(16) * 16 * L->NBLK + int64_t(L->Do) * L->NBLK * L->NBLK * 256;
 }
 

@@ -2,13 +2,11 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
-#include "cbfssm_gp_bwd.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPBWD_DECLARE)
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
 
 static int gp_bwd_maxwg(int NBLK)
 {
@@ -30,16 +28,6 @@ static int dispatch_gp_bwd(int NBLK, int DK, const GpBwdArgs& a, unsigned nwg, h
     return -3;
 }
 
-// the limits of cbfssm_gp_predict_f64, checked on the layout itself (a layout need not come from cbfssm_gp_pack_layout)
-static bool gp_bwd_layout_ok(const cbfssm_pack_layout* L)
-{
-    if (!L) return false;
-    if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
-    if (gp_bwd_maxwg(L->NBLK) == 0 || 16 * L->NBLK < L->M) return false;
-    if ((L->DK != 2 && L->DK != 4 && L->DK != 6) || 4 * L->DK < L->D) return false;
-    if (L->JB != (4 * L->DK + 1 + 15) / 16 || L->rev_slab <= 0 || (L->rev_stash != 0) != (L->NBLK > 7)) return false;
-    return true;
-}
 
 }  // namespace cbfssm
 
@@ -49,14 +37,14 @@ extern "C" {
 
 int64_t cbfssm_gp_predict_bwd_workgroups(const cbfssm_pack_layout* L, int64_t npts)
 {
-    if (!gp_bwd_layout_ok(L) || npts < 0 || npts > (int64_t(1) << 34)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT) || npts < 0 || npts > (int64_t(1) << 34)) return -1;
     const int64_t nblocks = (npts + 15) / 16, cap = gp_bwd_maxwg(L->NBLK);
     return nblocks < cap ? nblocks : cap;
 }
 
 int64_t cbfssm_gp_predict_bwd_work_elems(const cbfssm_pack_layout* L, int64_t npts)
 {
-    if (!gp_bwd_layout_ok(L) || npts < 0 || npts > (int64_t(1) << 34)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT) || npts < 0 || npts > (int64_t(1) << 34)) return -1;
     if (!L->rev_stash) return 0;
     const int64_t nblocks = (npts + 15) / 16;
     return 2 * nblocks * L->NBLK * 256 + cbfssm_stash_contract_work_elems(L, nblocks);
@@ -67,7 +55,7 @@ int cbfssm_gp_predict_bwd_f64(const cbfssm_pack_layout* L, const double* pack, c
                               double* gB_image, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_bwd_layout_ok(L))
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT))
         return fail(-3, "gp_predict_bwd limits: M <= %d, D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (npts < 0 || npts > (int64_t(1) << 34)) return fail(-1, "bad npts");
@@ -77,10 +65,7 @@ int cbfssm_gp_predict_bwd_f64(const cbfssm_pack_layout* L, const double* pack, c
     hipStream_t st = (hipStream_t)stream;
     GpBwdArgs a;
     memset(&a, 0, sizeof(a));
-    a.pk.Bp = pack + L->Bp; a.pk.Zp = pack + L->Zp; a.pk.cz = pack + L->cz; a.pk.muA = pack + L->muA; a.pk.s2A = pack + L->s2A;
-    a.pk.invl = pack + L->invl; a.pk.scal = pack + L->scal; a.pk.KSr = (L->M + 3) / 4;
-    a.pk.Wp = pack + L->Wp; a.pk.WTp = pack + L->WTp;
-    a.rk.muB = pack + L->muB; a.rk.s2B = pack + L->s2B; a.rk.ZT = pack + L->ZT;
+    gp_pack_ptrs(L, pack, a.pk, a.rk);
     a.X = X; a.gmean = gmean; a.gvar = gvar; a.gX = gX; a.gpart = gpart; a.slab = L->rev_slab;
     a.npts = npts; a.nblocks = (npts + 15) / 16;
     a.M = L->M; a.D = L->D; a.Do = L->Do;

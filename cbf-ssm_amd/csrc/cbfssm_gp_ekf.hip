@@ -4,16 +4,11 @@
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_ekf.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPEKF_DECLARE)
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
-
-// cbfssm_gp_lin.hip
-__global__ void gp_lin_alpha_kernel(const double* Kinv, const double* G, const double* muB, int M, int Do, int MP, int tri,
-                                    double* alpha);
 
 static int dispatch_gp_ekf(int NBLK, int DK, const GpEkfArgs& a, hipStream_t st)
 {
@@ -25,35 +20,12 @@ static int dispatch_gp_ekf(int NBLK, int DK, const GpEkfArgs& a, hipStream_t st)
     return -3;
 }
 
-static bool gp_ekf_nblk_ok(int NBLK)
-{
-    switch (NBLK) {
-#define X(NB) case NB: return true;
-        CBF_FOR_EACH_GPBWD_NBLK(X)
-#undef X
-    }
-    return false;
-}
-
-// the limits of cbfssm_gp_predict_f64, checked on the layout itself (as cbfssm_gp_linearize_f64 does), and D >= Do
-bool gp_ekf_layout_ok(const cbfssm_pack_layout* L)
-{
-    if (!L) return false;
-    if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
-    if (L->D < L->Do) return false;
-    if (!gp_ekf_nblk_ok(L->NBLK) || 16 * L->NBLK < L->M) return false;
-    if ((L->DK != 2 && L->DK != 4 && L->DK != 6) || 4 * L->DK < L->D) return false;
-    if (L->KS != 4 * L->NBLK) return false;
-    if (L->JB != (4 * L->DK + 1 + 15) / 16) return false;
-    return true;
-}
-
 // what cbfssm_gp_ekf_f64 and cbfssm_gp_eks_f64 (cbfssm_gp_eks.hip) refuse before they look at a pointer
 int gp_ekf_check_sizes(const char* who, const cbfssm_pack_layout* L, int Dy, int64_t N, int64_t T)
 {
     if (!L) return fail(-1, "null layout");
     if (N < 0 || T < 0 || Dy < 0) return fail(-1, "negative size");
-    if (!gp_ekf_layout_ok(L))
+    if (!gp_layout_ok(L, GP_NEED_STATE))
         return fail(-3, "%s limits: M <= %d, Do <= D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     who, CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (Dy < 1 || Dy > L->Do) return fail(-3, "%s: 1 <= Dy <= Do (Dy=%d Do=%d)", who, Dy, L->Do);
@@ -75,10 +47,7 @@ static int gp_ekf_launch_j(const char* who, const cbfssm_pack_layout* L, const d
     if (e != hipSuccess) return fail(-int(e) - 1000, "%s: alpha launch failed", who);
     GpEkfArgs k;
     memset(&k, 0, sizeof(k));
-    k.pk.Bp = pack + L->Bp; k.pk.Zp = pack + L->Zp; k.pk.cz = pack + L->cz; k.pk.muA = pack + L->muA;
-    k.pk.invl = pack + L->invl; k.pk.scal = pack + L->scal; k.pk.KSr = (L->M + 3) / 4;
-    k.pk.Wp = pack + L->Wp; k.pk.WTp = pack + L->WTp;
-    k.rk.muB = pack + L->muB; k.rk.s2B = pack + L->s2B; k.rk.ZT = pack + L->ZT;
+    gp_pack_ptrs(L, pack, k.pk, k.rk);
     k.m0 = m0; k.P0 = P0; k.a = a; k.y = y; k.cond = cond; k.var_x = var_x; k.var_y = var_y; k.alpha = work;
     k.means = means; k.covs = covs; k.loglik = loglik; k.pmeans = pmeans; k.pcovs = pcovs; k.cross = cross;
     k.N = int(N); k.T = int(T); k.M = L->M; k.D = L->D; k.Do = L->Do; k.Dy = Dy; k.tri = tri;
@@ -105,7 +74,7 @@ extern "C" {
 
 int64_t cbfssm_gp_ekf_work_elems(const cbfssm_pack_layout* L)
 {
-    if (!gp_ekf_layout_ok(L)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_STATE)) return -1;
     return int64_t(16) * 16 * L->NBLK;
 }
 

@@ -9,9 +9,10 @@
 //       m- <- m- + P-[:, j] delta / s;  P-[i][k] <- P-[i][k] - (P-[i][j] P-[k][j]) / s;  loglik[n] -= (log(2 pi s) + delta^2 / s) / 2
 //   m, P <- m-, P-;  means[t][n] = m;  covs[t][n] = P
 //
-// The GP part of a step is gp_linearize_kernel (cbfssm_gp_lin.hpp) without its variance Jacobian, as a copy: the wave
-// layout GpBwdCfg<NBLK>, the kernel tile, A2 and fvar0 in the form layout->gp_form asks for, per output dimension d
-// Em_d = alpha_d o k and its (Z~)^T product, the waves' partial tiles summed in a fixed order.  What differs:
+// The GP part of a step is that of gp_linearize_kernel (cbfssm_gp_lin.hpp) without its variance Jacobian: the wave layout
+// GpBwdCfg<NBLK> and, from the shared body (cbfssm_gp_tile.hpp, GpWave), the row-block setup, the kernel tile (phase B), A2
+// and fvar0 in the form layout->gp_form asks for; per output dimension d Em_d = alpha_d o k and its (Z~)^T product, the
+// waves' partial tiles summed in a fixed order.  What differs:
 //
 //   - one workgroup owns 16 chains for all T steps (the column block is fixed, the time loop is inside, as in
 //     gp_rollout_kernel); the scaled GP input of the next step is written straight into the LDS operand tile xq;
@@ -81,53 +82,6 @@ struct GpEkfGeom {
     static_assert(LDS_DOUBLES <= 163840 / 8, "LDS budget");
 };
 
-// out[i] = (rows of the A-operand image behind aop[i]) x (the [16 NBLK][17] tile in LDS): lin_image_times_tile, as a copy
-template <int RB>
-__device__ __forceinline__ void ekf_image_times_tile(const double* const (&aop)[RB], const bool (&ok)[RB], const double* tile,
-                                                     int KSr, int g, int nl, d4 (&out)[RB])
-{
-    constexpr int PD = 17;
-    d4 acc[RB][2];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) { acc[i][0] = d4{0, 0, 0, 0}; acc[i][1] = d4{0, 0, 0, 0}; }
-#pragma unroll 1
-    for (int s0 = 0; s0 < KSr; s0 += 4) {
-        double b[4], av[RB][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int i = 0; i < RB; ++i) av[i][j] = aop[i][(s0 + j) * 64];
-            b[j] = tile[(4 * (s0 + j) + g) * PD + nl];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-                if (ok[i]) acc[i][j & 1] = CBF_MFMA(av[i][j], b[j], acc[i][j & 1]);
-    }
-#pragma unroll
-    for (int i = 0; i < RB; ++i) out[i] = acc[i][0] + acc[i][1];
-}
-
-// the same product with the wave's K^-1 rows held in VGPRs (one row block per wave, up to seven row blocks)
-template <int KS>
-__device__ __forceinline__ d4 ekf_regs_times_tile(const double (&br)[KS], const double* tile, int KSr, int g, int nl)
-{
-    constexpr int PD = 17;
-    d4 acc[2] = {d4{0, 0, 0, 0}, d4{0, 0, 0, 0}};
-#pragma unroll
-    for (int s0 = 0; s0 < KS; s0 += 4) {
-        if (s0 < KSr) {
-            double b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = tile[(4 * (s0 + j) + g) * PD + nl];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j & 1] = CBF_MFMA(br[s0 + j], b[j], acc[j & 1]);
-        }
-    }
-    return acc[0] + acc[1];
-}
-
 // per (chain, row) lane of the covariance part: what it carries from step to step
 struct EkfLane {
     double m, lin;
@@ -142,7 +96,8 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
 {
     constexpr bool BREG = (RB == 1);                    // K^-1 rows of the wave in VGPRs (2 KS = 8 NBLK <= 56 registers)
     typedef GpEkfGeom<NBLK, DK> G;
-    constexpr int W = (NBLK + RB - 1) / RB, NT = 64 * W, MP = 16 * NBLK, KS = MP / 4;
+    typedef GpWave<NBLK, RB, DK, BREG> WV;
+    constexpr int W = WV::W, NT = WV::NT, MP = WV::MP;
     constexpr int JB = G::JB, PD = G::PD, PT = G::PT, PW = G::PW, CT = G::CT;
     constexpr int TPT = (256 + NT - 1) / NT;            // (chain, row) lanes per thread: 4, 2 or 1
 
@@ -161,41 +116,13 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, nl = l & 15;
     const int M = a.M, D = a.D, Do = a.Do, Dy = a.Dy, N = a.N, T = a.T;
     const int naux = D - Do;
-    const int KSr = a.pk.KSr;
     const int c0 = blockIdx.x * 16;
     const double sig2 = a.pk.scal[CBFSSM_SCAL_SIGMA2];
 
-    bool ok[RB];
-    int rbs[RB];
-    double Zreg[RB][DK], czr[RB][4];
-    const double *bop[RB], *wop[RB], *wtop[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        ok[i] = (w * RB + i) < NBLK;
-        rbs[i] = ok[i] ? (w * RB + i) : (NBLK - 1);
-#pragma unroll
-        for (int s = 0; s < DK; ++s) Zreg[i][s] = a.pk.Zp[(rbs[i] * DK + s) * 64 + l];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) czr[i][r] = a.pk.cz[16 * rbs[i] + 4 * r + g];
-        bop[i] = a.pk.Bp + rbs[i] * KS * 64 + l;
-        wop[i] = a.pk.Wp + rbs[i] * KS * 64 + l;
-        wtop[i] = a.pk.WTp + rbs[i] * KS * 64 + l;
-    }
-    double breg[BREG ? KS : 1];
-    if constexpr (BREG) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s) breg[s] = bop[0][s * 64];
-    }
-    // the wave's (Z / l)^T operands, loop invariant: in VGPRs beside the K^-1 rows, else re-read (L2) per output dimension
-    double ztr[BREG ? JB * 4 : 1];
-    if constexpr (BREG) {
-#pragma unroll
-        for (int q = 0; q < JB * 4; ++q) ztr[q] = a.rk.ZT[rbs[0] * JB * 256 + q * 64 + l];
-    }
-    auto kinv_times = [&](const double* tile, d4 (&out)[RB]) {
-        if constexpr (BREG) out[0] = ekf_regs_times_tile<KS>(breg, tile, KSr, g, nl);
-        else ekf_image_times_tile<RB>(bop, ok, tile, KSr, g, nl, out);
-    };
+    WV wv;
+    wv.setup(a.pk, tid);
+    wv.setup_forms(a.pk);
+    wv.hold_kinv(a.rk);                                 // BREG: the wave's K^-1 rows and (Z / l)^T operands in VGPRs
     // of the (Z~)^T E tile the state rows (first input row block) and the ones row D are used
     const bool jb_used1 = D >= 16;
 
@@ -252,64 +179,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
             cnd[k2] = a.cond ? a.cond[tc] : 1.0;
         }
 
-        // ---- kernel tile (rows of this wave); rows m >= M are exactly zero
+        // ---- kernel tile (rows of this wave): the shared phase B
         d4 kreg[RB];
-        {
-            double bx[DK], xx = 0.0;
-#pragma unroll
-            for (int s = 0; s < DK; ++s) {
-                bx[s] = xq[(4 * s + g) * PD + nl];
-                xx = fma(bx[s], bx[s], xx);
-            }
-            xx += __shfl_xor(xx, 16);
-            xx += __shfl_xor(xx, 32);
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                kreg[i] = d4{0, 0, 0, 0};
-                if (ok[i]) {
-                    d4 e;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r] = czr[i][r] - 0.5 * xx;
-#pragma unroll
-                    for (int s = 0; s < DK; ++s) e = CBF_MFMA(Zreg[i][s], bx[s], e);
-                    e = tile_exp4(e);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        kreg[i][r] = (16 * rbs[i] + 4 * r + g < M) ? e[r] : 0.0;
-                        Kt[(16 * rbs[i] + 4 * r + g) * PD + nl] = kreg[i][r];
-                    }
-                }
-            }
-        }
+        wv.kernel_tile(xq, Kt, M, kreg);
         __syncthreads();
 
-        // ---- A2 of this wave's rows and this wave's part of sigma^2 - fvar0
+        // ---- A2 of this wave's rows and this wave's part of sigma^2 - fvar0: the shared A2 step
         d4 a2[RB];
-        double v0 = 0.0;
-        if (a.tri) {
-            d4 A[RB];
-            ekf_image_times_tile<RB>(wop, ok, Kt, KSr, g, nl, A);
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                if (ok[i]) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v0 = fma(A[i][r], A[i][r], v0);
-                        A2t[(16 * rbs[i] + g + 4 * r) * PD + nl] = A[i][r];
-                    }
-                }
-            }
-            __syncthreads();
-            ekf_image_times_tile<RB>(wtop, ok, A2t, KSr, g, nl, a2);
-        } else {
-            kinv_times(Kt, a2);
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v0 = fma(kreg[i][r], a2[i][r], v0);
-        }
-        v0 += __shfl_xor(v0, 16);
-        v0 += __shfl_xor(v0, 32);
+        const double v0 = gp_sum_groups(wv.a2_forms(a.tri, Kt, A2t, kreg, a2));
         if (g == 0) red0[w * 16 + nl] = v0;
         __syncthreads();                                // every wave is done reading the kernel tile and A: both are free
 
@@ -318,8 +195,8 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
         auto fetch = [&](int d) {
 #pragma unroll
             for (int i = 0; i < RB; ++i) {
-                const double* sBp = a.rk.s2B + rbs[i] * 256 + (d >> 2) * 64 + 16 * (d & 3) + g;   // s2[16 rb + g + 4 r][d]
-                const double* alp = a.alpha + d * MP + 16 * rbs[i] + g;
+                const double* sBp = a.rk.s2B + wv.rbs[i] * 256 + (d >> 2) * 64 + 16 * (d & 3) + g;   // s2[16 rb + g + 4 r][d]
+                const double* alp = a.alpha + d * MP + 16 * wv.rbs[i] + g;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { aln[i][r] = alp[4 * r]; s2n[i][r] = sBp[4 * r]; }
             }
@@ -334,14 +211,13 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
             for (int i = 0; i < RB; ++i) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const double u = ok[i] ? a2[i][r] * s2n[i][r] : 0.0;
+                    const double u = wv.ok[i] ? a2[i][r] * s2n[i][r] : 0.0;
                     em[i][r] = aln[i][r] * kreg[i][r];
                     vs = fma(a2[i][r], u, vs);
                 }
             }
             if (d + 1 < Do) fetch(d + 1);
-            vs += __shfl_xor(vs, 16);
-            vs += __shfl_xor(vs, 32);
+            vs = gp_sum_groups(vs);
             __syncthreads();                            // the previous dimension's partial tiles are read
 
             // 2: the partial ZT products of Em_d over this wave's rows
@@ -353,14 +229,14 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_ekf_kernel(GpE
                 for (int jb = 0; jb < JB; ++jb) xm[jb] = d4{0, 0, 0, 0};
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
-                    if (ok[i]) {
-                        const double* ZTp = a.rk.ZT + rbs[i] * JB * 256 + l;
+                    if (wv.ok[i]) {
+                        const double* ZTp = a.rk.ZT + wv.rbs[i] * JB * 256 + l;
 #pragma unroll
                         for (int jb = 0; jb < JB; ++jb) {
                             if (jb == 0 || jb_used1) {
 #pragma unroll
                                 for (int r = 0; r < 4; ++r)
-                                    xm[jb] = CBF_MFMA(BREG ? ztr[jb * 4 + r] : ZTp[(jb * 4 + r) * 64], em[i][r], xm[jb]);   // rows j, k = m
+                                    xm[jb] = CBF_MFMA(BREG ? wv.ztr[jb * 4 + r] : ZTp[(jb * 4 + r) * 64], em[i][r], xm[jb]);   // rows j, k = m
                             }
                         }
                     }

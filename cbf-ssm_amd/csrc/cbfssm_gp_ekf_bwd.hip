@@ -4,19 +4,11 @@
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_ekf_bwd.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPEKFBWD_DECLARE)
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
-
-// cbfssm_gp_lin.hip
-__global__ void gp_lin_alpha_kernel(const double* Kinv, const double* G, const double* muB, int M, int Do, int MP, int tri,
-                                    double* alpha);
-// cbfssm_gp_ekf.hip
-bool gp_ekf_layout_ok(const cbfssm_pack_layout* L);
-int gp_ekf_check_sizes(const char* who, const cbfssm_pack_layout* L, int Dy, int64_t N, int64_t T);
 
 static int dispatch_gp_ekf_bwd(int NBLK, int DK, const GpEkfBwdArgs& a, hipStream_t st)
 {
@@ -28,14 +20,9 @@ static int dispatch_gp_ekf_bwd(int NBLK, int DK, const GpEkfBwdArgs& a, hipStrea
     return -3;
 }
 
-// the filter's limits and what the adjoint needs of the layout: a slab, and stash mode exactly above seven row blocks
-static bool gp_ekf_bwd_layout_ok(const cbfssm_pack_layout* L)
-{
-    if (!gp_ekf_layout_ok(L)) return false;
-    if (L->rev_slab <= 0 || (L->rev_stash != 0) != (L->NBLK > 7)) return false;
-    if (L->gp_form != CBFSSM_GP_FORM_DENSE && L->gp_form != CBFSSM_GP_FORM_TRI) return false;
-    return true;
-}
+// the filter's limits (Do <= D) and what the adjoint needs of the layout: a slab, stash mode exactly above seven row
+// blocks, a GP form
+static const unsigned kNeeds = GP_NEED_ADJOINT | GP_NEED_FORM | GP_NEED_STATE;
 
 // work: alpha | Pb rows | Jh | stash_a | stash_k | contraction scratch
 static int64_t ekf_bwd_fixed_elems(const cbfssm_pack_layout* L, int64_t groups)
@@ -51,13 +38,13 @@ extern "C" {
 
 int64_t cbfssm_gp_ekf_bwd_workgroups(const cbfssm_pack_layout* L, int64_t N)
 {
-    if (!gp_ekf_bwd_layout_ok(L) || N < 0 || N > (int64_t(1) << 30)) return -1;
+    if (!gp_layout_ok(L, kNeeds) || N < 0 || N > (int64_t(1) << 30)) return -1;
     return (N + 15) / 16;
 }
 
 int64_t cbfssm_gp_ekf_bwd_work_elems(const cbfssm_pack_layout* L, int64_t N, int64_t T)
 {
-    if (!gp_ekf_bwd_layout_ok(L) || N < 0 || N > (int64_t(1) << 30) || T < 0 || T > (int64_t(1) << 24)) return -1;
+    if (!gp_layout_ok(L, kNeeds) || N < 0 || N > (int64_t(1) << 30) || T < 0 || T > (int64_t(1) << 24)) return -1;
     const int64_t groups = (N + 15) / 16;
     int64_t n = ekf_bwd_fixed_elems(L, groups);
     if (L->rev_stash) {
@@ -75,7 +62,7 @@ int cbfssm_gp_ekf_bwd_f64(const cbfssm_pack_layout* L, const double* pack, const
                           double* gpart, double* work, double* gB_image, void* stream)
 {
     if (int rc = gp_ekf_check_sizes("gp_ekf_bwd", L, Dy, N, T)) return rc;
-    if (!gp_ekf_bwd_layout_ok(L)) return fail(-3, "gp_ekf_bwd: the layout has no adjoint (rev_slab, rev_stash, gp_form)");
+    if (!gp_layout_ok(L, kNeeds)) return fail(-3, "gp_ekf_bwd: the layout has no adjoint (rev_slab, rev_stash, gp_form)");
     if (!pack || !m0 || !y || !var_y || !means || !covs || !pmeans || !pcovs || !cross || !jac || !gm0 || !gy || !gpart || !work)
         return fail(-1, "gp_ekf_bwd: null pointer");
     if (L->D > L->Do && (!a || !ga)) return fail(-1, "gp_ekf_bwd: D=%d > Do=%d needs a and ga", L->D, L->Do);
@@ -91,10 +78,7 @@ int cbfssm_gp_ekf_bwd_f64(const cbfssm_pack_layout* L, const double* pack, const
     const int64_t groups = (N + 15) / 16;
     GpEkfBwdArgs g;
     memset(&g, 0, sizeof(g));
-    g.pk.Bp = pack + L->Bp; g.pk.Zp = pack + L->Zp; g.pk.cz = pack + L->cz; g.pk.muA = pack + L->muA; g.pk.s2A = pack + L->s2A;
-    g.pk.invl = pack + L->invl; g.pk.scal = pack + L->scal; g.pk.KSr = (L->M + 3) / 4;
-    g.pk.Wp = pack + L->Wp; g.pk.WTp = pack + L->WTp;
-    g.rk.muB = pack + L->muB; g.rk.s2B = pack + L->s2B; g.rk.ZT = pack + L->ZT;
+    gp_pack_ptrs(L, pack, g.pk, g.rk);
     g.m0 = m0; g.a = a; g.y = y; g.cond = cond; g.var_y = var_y; g.alpha = work;
     g.means = means; g.pmeans = pmeans; g.pcovs = pcovs; g.cross = cross; g.jac = jac;
     g.gmeans = gmeans; g.gcovs = gcovs; g.gloglik = gloglik;

@@ -4,18 +4,9 @@
 #include <hip/hip_runtime.h>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_eks.hpp"
+#include "cbfssm_gp_host.hpp"
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
-
-// cbfssm_gp_ekf.hip
-bool gp_ekf_layout_ok(const cbfssm_pack_layout* L);
-int gp_ekf_check_sizes(const char* who, const cbfssm_pack_layout* L, int Dy, int64_t N, int64_t T);
-int gp_ekf_launch(const char* who, const cbfssm_pack_layout* L, const double* pack, const double* m0, const double* P0,
-                  const double* a, const double* y, const double* cond, const double* var_x, const double* var_y, int Dy,
-                  int64_t N, int64_t T, double* means, double* covs, double* loglik, double* pmeans, double* pcovs,
-                  double* cross, double* work, hipStream_t st);
 
 // the two smoother launches behind a forward pass that left means, covs, pmeans, pcovs and cross (also behind GPModel.adf:
 // cbfssm_gp_adf.hip)
@@ -46,7 +37,7 @@ extern "C" {
 
 int64_t cbfssm_gp_eks_work_elems(const cbfssm_pack_layout* L)
 {
-    if (!gp_ekf_layout_ok(L)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_STATE)) return -1;
     return int64_t(16) * 16 * L->NBLK;                  // alpha = K^-1 mu of the forward kernel; the sweep needs none
 }
 

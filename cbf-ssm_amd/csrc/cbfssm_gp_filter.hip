@@ -3,15 +3,16 @@
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_filter.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPFILT_DECLARE)
 
 namespace cbfssm {
 
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
-
 static const int64_t kMaxChains = int64_t(1) << 30;    // as the pass kernels
 static const int64_t kMaxSteps = int64_t(1) << 24;
+// of the layout: the adjoint's fields (the forward asks for them too), a GP form, Do <= D
+static const unsigned kNeeds = GP_NEED_ADJOINT | GP_NEED_FORM | GP_NEED_STATE;
 
 static int dispatch_gp_filt(int NBLK, int DK, const GpFiltArgs& a, hipStream_t st)
 {
@@ -33,27 +34,11 @@ static int dispatch_gp_filt_bwd(int NBLK, int DK, const GpFiltBwdArgs& a, hipStr
     return -3;
 }
 
-// the limits of cbfssm_gp_predict_f64, checked on the layout itself (a layout need not come from cbfssm_gp_pack_layout)
-static bool gp_filt_layout_ok(const cbfssm_pack_layout* L)
-{
-    if (!L) return false;
-    if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
-    if (L->Do > L->D) return false;
-    bool nb = false;
-#define X(NB) nb = nb || (L->NBLK == NB);
-    CBF_FOR_EACH_GPBWD_NBLK(X)
-#undef X
-    if (!nb || 16 * L->NBLK < L->M || L->KS != 4 * L->NBLK) return false;
-    if ((L->DK != 2 && L->DK != 4 && L->DK != 6) || 4 * L->DK < L->D) return false;
-    if (L->JB != (4 * L->DK + 1 + 15) / 16 || L->rev_slab <= 0 || (L->rev_stash != 0) != (L->NBLK > 7)) return false;
-    if (L->gp_form != CBFSSM_GP_FORM_DENSE && L->gp_form != CBFSSM_GP_FORM_TRI) return false;
-    return true;
-}
 
 static int check_sizes(const cbfssm_pack_layout* L, int64_t N, int64_t T, const char* who)
 {
     if (!L) return fail(-1, "%s: null layout", who);
-    if (!gp_filt_layout_ok(L))
+    if (!gp_layout_ok(L, kNeeds))
         return fail(-3, "%s limits: M <= %d, Do <= D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     who, CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (N < 0 || T < 1) return fail(-1, "%s: N=%lld must be >= 0 and T=%lld >= 1", who, (long long)N, (long long)T);
@@ -63,9 +48,7 @@ static int check_sizes(const cbfssm_pack_layout* L, int64_t N, int64_t T, const 
 
 static void set_pack(PackPtrs& pk, const cbfssm_pack_layout* L, const double* pack)
 {
-    pk.Bp = pack + L->Bp; pk.Zp = pack + L->Zp; pk.cz = pack + L->cz; pk.muA = pack + L->muA; pk.s2A = pack + L->s2A;
-    pk.invl = pack + L->invl; pk.scal = pack + L->scal; pk.KSr = (L->M + 3) / 4;
-    pk.Wp = pack + L->Wp; pk.WTp = pack + L->WTp;
+    gp_pack_ptrs(L, pack, pk);
 }
 
 }  // namespace cbfssm
@@ -76,19 +59,19 @@ extern "C" {
 
 int64_t cbfssm_gp_filter_partials(const cbfssm_pack_layout* L, int64_t N)
 {
-    if (!gp_filt_layout_ok(L) || N < 0 || N > kMaxChains) return -1;
+    if (!gp_layout_ok(L, kNeeds) || N < 0 || N > kMaxChains) return -1;
     return (N + 15) / 16;
 }
 
 int64_t cbfssm_gp_filter_bwd_workgroups(const cbfssm_pack_layout* L, int64_t N)
 {
-    if (!gp_filt_layout_ok(L) || N < 0 || N > kMaxChains) return -1;
+    if (!gp_layout_ok(L, kNeeds) || N < 0 || N > kMaxChains) return -1;
     return (N + 15) / 16;
 }
 
 int64_t cbfssm_gp_filter_bwd_work_elems(const cbfssm_pack_layout* L, int64_t N, int64_t T)
 {
-    if (!gp_filt_layout_ok(L) || N < 0 || N > kMaxChains || T < 0 || T > kMaxSteps) return -1;
+    if (!gp_layout_ok(L, kNeeds) || N < 0 || N > kMaxChains || T < 0 || T > kMaxSteps) return -1;
     if (!L->rev_stash) return 0;
     const int64_t nslots = (N + 15) / 16 * T;
     return 2 * nslots * L->NBLK * 256 + cbfssm_stash_contract_work_elems(L, nslots);

@@ -7,12 +7,11 @@
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_fullq.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPFQ_DECLARE)
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
 
 static int gp_fq_maxwg(int NBLK)
 {
@@ -42,18 +41,6 @@ static int dispatch_gp_fq_fwd(int NBLK, int DK, const GpFqFwdArgs& a, unsigned n
 #undef X
     }
     return -3;
-}
-
-// the limits of cbfssm_gp_predict_f64, checked on the layout itself (as cbfssm_gp_predict_bwd_f64 does)
-static bool gp_fq_layout_ok(const cbfssm_pack_layout* L)
-{
-    if (!L) return false;
-    if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
-    if (gp_fq_maxwg(L->NBLK) == 0 || 16 * L->NBLK < L->M) return false;
-    if ((L->DK != 2 && L->DK != 4 && L->DK != 6) || 4 * L->DK < L->D) return false;
-    if (L->KS != 4 * L->NBLK) return false;
-    if (L->JB != (4 * L->DK + 1 + 15) / 16 || L->rev_slab <= 0 || (L->rev_stash != 0) != (L->NBLK > 7)) return false;
-    return true;
 }
 
 static bool npts_ok(int64_t npts) { return npts >= 0 && npts <= (int64_t(1) << 34); }
@@ -226,14 +213,14 @@ extern "C" {
 
 int64_t cbfssm_gp_fullq_pack_elems(const cbfssm_pack_layout* L)
 {
-    if (!gp_fq_layout_ok(L)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT)) return -1;
     return fq_image_elems(L) + fq_dense_elems(L) + int64_t(L->M) * L->M;
 }
 
 int cbfssm_gp_fullq_prepare_f64(const cbfssm_pack_layout* L, const double* q_sqrt, double* qpack, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_fq_layout_ok(L))
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT))
         return fail(-3, "gp_fullq limits: M <= %d, D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (!q_sqrt || !qpack) return fail(-1, "null pointer");
@@ -254,7 +241,7 @@ int cbfssm_gp_fullq_predict_f64(const cbfssm_pack_layout* L, const double* pack,
                                 int64_t npts, double* fmean, double* fvar, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_fq_layout_ok(L))
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT))
         return fail(-3, "gp_fullq_predict limits: M <= %d, D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (!npts_ok(npts)) return fail(-1, "bad npts");
@@ -262,9 +249,7 @@ int cbfssm_gp_fullq_predict_f64(const cbfssm_pack_layout* L, const double* pack,
     if (npts == 0) return 0;
     GpFqFwdArgs a;
     memset(&a, 0, sizeof(a));
-    a.pk.Bp = pack + L->Bp; a.pk.Zp = pack + L->Zp; a.pk.cz = pack + L->cz; a.pk.muA = pack + L->muA;
-    a.pk.invl = pack + L->invl; a.pk.scal = pack + L->scal; a.pk.KSr = (L->M + 3) / 4;
-    a.pk.Wp = pack + L->Wp; a.pk.WTp = pack + L->WTp;
+    gp_pack_ptrs(L, pack, a.pk);
     a.X = X; a.Sp = qpack; a.fmean = fmean; a.fvar = fvar;
     a.npts = npts; a.nblocks = (npts + 15) / 16;
     a.M = L->M; a.D = L->D; a.Do = L->Do; a.tri = (L->gp_form == CBFSSM_GP_FORM_TRI);
@@ -279,7 +264,7 @@ int cbfssm_gp_fullq_kl_f64(const cbfssm_pack_layout* L, const double* pack, cons
                            const double* zeta_mean, double* kl, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_fq_layout_ok(L)) return fail(-3, "gp_fullq limits: M <= %d, D <= 24, Do <= %d", CBFSSM_MAX_M, CBFSSM_MAX_DOUT);
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT)) return fail(-3, "gp_fullq limits: M <= %d, D <= 24, Do <= %d", CBFSSM_MAX_M, CBFSSM_MAX_DOUT);
     if (!pack || !q_sqrt || !qpack || !zeta_mean || !kl) return fail(-1, "null pointer");
     const double* Ssum = qpack + fq_image_elems(L) + fq_dense_elems(L);
     hipLaunchKernelGGL(fq_kl_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, q_sqrt, Ssum, pack + L->Kinv, zeta_mean,
@@ -289,20 +274,20 @@ int cbfssm_gp_fullq_kl_f64(const cbfssm_pack_layout* L, const double* pack, cons
 
 int64_t cbfssm_gp_fullq_bwd_workgroups(const cbfssm_pack_layout* L, int64_t npts)
 {
-    if (!gp_fq_layout_ok(L) || !npts_ok(npts)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT) || !npts_ok(npts)) return -1;
     const int64_t nblocks = (npts + 15) / 16, cap = gp_fq_maxwg(L->NBLK);
     return nblocks < cap ? nblocks : cap;
 }
 
 int64_t cbfssm_gp_fullq_a2_elems(const cbfssm_pack_layout* L, int64_t npts)
 {
-    if (!gp_fq_layout_ok(L) || !npts_ok(npts)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT) || !npts_ok(npts)) return -1;
     return (npts + 15) / 16 * L->NBLK * 256;
 }
 
 int64_t cbfssm_gp_fullq_bwd_work_elems(const cbfssm_pack_layout* L, int64_t npts)
 {
-    if (!gp_fq_layout_ok(L) || !npts_ok(npts)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT) || !npts_ok(npts)) return -1;
     if (!L->rev_stash) return 0;
     const int64_t nblocks = (npts + 15) / 16;
     return 2 * nblocks * L->NBLK * 256 + cbfssm_stash_contract_work_elems(L, nblocks);
@@ -313,7 +298,7 @@ int cbfssm_gp_fullq_bwd_f64(const cbfssm_pack_layout* L, const double* pack, con
                             double* gB_image, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_fq_layout_ok(L))
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT))
         return fail(-3, "gp_fullq_bwd limits: M <= %d, D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (!npts_ok(npts)) return fail(-1, "bad npts");
@@ -323,9 +308,7 @@ int cbfssm_gp_fullq_bwd_f64(const cbfssm_pack_layout* L, const double* pack, con
     hipStream_t st = (hipStream_t)stream;
     GpFqArgs a;
     memset(&a, 0, sizeof(a));
-    a.pk.Bp = pack + L->Bp; a.pk.Zp = pack + L->Zp; a.pk.cz = pack + L->cz; a.pk.muA = pack + L->muA;
-    a.pk.invl = pack + L->invl; a.pk.scal = pack + L->scal; a.pk.KSr = (L->M + 3) / 4;
-    a.rk.muB = pack + L->muB; a.rk.ZT = pack + L->ZT;               // (no sigma_z^2 images: the full form has none)
+    gp_pack_ptrs(L, pack, a.pk, a.rk);                              // (the full form reads no sigma_z^2 image)
     a.X = X; a.gmean = gmean; a.gvar = gvar; a.gX = gX; a.gpart = gpart; a.slab = L->rev_slab;
     a.npts = npts; a.nblocks = (npts + 15) / 16;
     a.Sp = qpack; a.a2img = a2_image;
@@ -346,7 +329,7 @@ int cbfssm_gp_fullq_bwd_f64(const cbfssm_pack_layout* L, const double* pack, con
 
 int64_t cbfssm_gp_fullq_wd_work_elems(const cbfssm_pack_layout* L, int64_t npts)
 {
-    if (!gp_fq_layout_ok(L) || !npts_ok(npts)) return -1;
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT) || !npts_ok(npts)) return -1;
     const int64_t ntp = int64_t(L->NBLK) * (L->NBLK + 1) / 2;
     return int64_t(fq_slices((npts + 15) / 16)) * L->Do * ntp * 256;
 }
@@ -355,7 +338,7 @@ int cbfssm_gp_fullq_wd_f64(const cbfssm_pack_layout* L, const double* a2_image, 
                            double* W, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_fq_layout_ok(L)) return fail(-3, "gp_fullq limits: M <= %d, D <= 24, Do <= %d", CBFSSM_MAX_M, CBFSSM_MAX_DOUT);
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT)) return fail(-3, "gp_fullq limits: M <= %d, D <= 24, Do <= %d", CBFSSM_MAX_M, CBFSSM_MAX_DOUT);
     if (!npts_ok(npts)) return fail(-1, "bad npts");
     if (!a2_image || !gvar || !work || !W) return fail(-1, "null pointer");
     if (npts == 0) return 0;
@@ -375,7 +358,7 @@ int cbfssm_gp_fullq_lbar_f64(const cbfssm_pack_layout* L, const double* pack, co
                              double kl_weight, double* gq, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_fq_layout_ok(L)) return fail(-3, "gp_fullq limits: M <= %d, D <= 24, Do <= %d", CBFSSM_MAX_M, CBFSSM_MAX_DOUT);
+    if (!gp_layout_ok(L, GP_NEED_ADJOINT)) return fail(-3, "gp_fullq limits: M <= %d, D <= 24, Do <= %d", CBFSSM_MAX_M, CBFSSM_MAX_DOUT);
     if (!q_sqrt || !gq || (!W && !pack)) return fail(-1, "null pointer");
     const unsigned nb = unsigned((L->M + 15) / 16);
     hipLaunchKernelGGL(fq_lbar_kernel, dim3(nb, nb, unsigned(L->Do)), dim3(16, 16), 0, (hipStream_t)stream, q_sqrt, W,

@@ -3,8 +3,8 @@
 //
 //   fvar[n][d] = sigma^2 - k_n^T a_n + a_n^T S_d a_n,   a_n = K^-1 k_n
 //
-// This is gp_predict_bwd_kernel (cbfssm_gp_bwd.hpp) as a copy -- that kernel keeps its code -- with one term of phase E
-// replaced and one result added:
+// This is gp_predict_bwd_kernel (cbfssm_gp_bwd.hpp) on the same shared phases (cbfssm_gp_tile.hpp: setup, B, C, F, the
+// slab; of E the transposes and the Kinvbar step), with one term of phase E replaced and one result added, which are its own:
 //
 //   D'  A2 of the whole block -> LDS (every wave needs all rows) and -> one C-layout image per column block, from
 //       which cbfssm_gp_fullq_wd_f64 forms W_d = sum_n Fv[n][d] a_n a_n^T afterwards
@@ -51,13 +51,13 @@ struct GpFqGeom {
 template <int NBLK, int RB, int DK, bool STASH>
 __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_bwd_kernel(GpFqArgs a)
 {
-    constexpr int W = (NBLK + RB - 1) / RB, NT = 64 * W, MP = 16 * NBLK, KS = MP / 4;
-    constexpr int JB = (4 * DK + 1 + 15) / 16;
+    typedef GpWave<NBLK, RB, DK> WV;
+    constexpr int W = WV::W, NT = WV::NT, MP = WV::MP;
+    constexpr int JB = WV::JB;
     constexpr int NG = 4 * JB;                          // 4-row groups of the input-adjoint tile
     constexpr int GPW = (NG + W - 1) / W;               // groups per wave in phase G
     constexpr int PD = 17;
     constexpr int PSL = JB * 256;
-    typedef Slab<NBLK, JB, STASH> SL;
 
     extern __shared__ double lds[];
     double* xq = lds;                                   // [4 DK][17] scaled inputs x~[j][n]
@@ -70,35 +70,13 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_bwd_kern
 
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, nl = l & 15;
     const int M = a.M, D = a.D, Do = a.Do;
-    const int KSr = a.pk.KSr;
 
-    bool ok[RB];
-    int rbs[RB];
-    double Zreg[RB][DK], czr[RB][4];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        ok[i] = (w * RB + i) < NBLK;
-        rbs[i] = ok[i] ? (w * RB + i) : (NBLK - 1);
-#pragma unroll
-        for (int s = 0; s < DK; ++s) Zreg[i][s] = a.pk.Zp[(rbs[i] * DK + s) * 64 + l];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) czr[i][r] = a.pk.cz[16 * rbs[i] + 4 * r + g];
-    }
-    const double* bop[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) bop[i] = a.pk.Bp + rbs[i] * KS * 64 + l;
+    WV wv;
+    wv.setup(a.pk, tid);
 
     // ---- accumulators of the parameter adjoints (all column blocks of this workgroup)
-    constexpr int NCB = STASH ? 1 : NBLK;
-    d4 gMu[RB], gZ[RB][JB], gB[RB][NCB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        gMu[i] = d4{0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < JB; ++j) gZ[i][j] = d4{0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) gB[i][j] = d4{0, 0, 0, 0};
-    }
+    GpAdjAcc<NBLK, RB, JB, STASH> acc;
+    acc.zero();                                         // (gS2 stays zero: no diagonal sigma_z^2 in the full form)
     double glx[GPW];
 #pragma unroll
     for (int k2 = 0; k2 < GPW; ++k2) glx[k2] = 0.0;
@@ -131,69 +109,21 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_bwd_kern
         }
         __syncthreads();
 
-        // ---- B: kernel tile (rows of this wave); rows m >= M are exactly zero
+        // ---- B: kernel tile (rows of this wave)
         d4 kreg[RB];
-        {
-            double bx[DK], xx = 0.0;
-#pragma unroll
-            for (int s = 0; s < DK; ++s) {
-                bx[s] = xq[(4 * s + g) * PD + nl];
-                xx = fma(bx[s], bx[s], xx);
-            }
-            xx += __shfl_xor(xx, 16);
-            xx += __shfl_xor(xx, 32);
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                kreg[i] = d4{0, 0, 0, 0};
-                if (ok[i]) {
-                    d4 e;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r] = czr[i][r] - 0.5 * xx;
-#pragma unroll
-                    for (int s = 0; s < DK; ++s) e = CBF_MFMA(Zreg[i][s], bx[s], e);
-                    e = tile_exp4(e);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        kreg[i][r] = (16 * rbs[i] + 4 * r + g < M) ? e[r] : 0.0;
-                        Kt[(16 * rbs[i] + 4 * r + g) * PD + nl] = kreg[i][r];
-                    }
-                }
-            }
-        }
+        wv.kernel_tile(xq, Kt, M, kreg);
         __syncthreads();
 
-        // ---- C: A2 rows of this wave.  K^-1 streams from L2 as the A-operand image of the pack (zero padded to KS
-        // k-steps): the operand loads of four k-steps are issued together, ahead of their MFMAs
+        // ---- C: A2 rows of this wave (K^-1 streams from L2 as the A-operand image of the pack)
         d4 a2[RB];
-        {
-            d4 acc[RB][2];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) { acc[i][0] = d4{0, 0, 0, 0}; acc[i][1] = d4{0, 0, 0, 0}; }
-#pragma unroll 1
-            for (int s0 = 0; s0 < KSr; s0 += 4) {
-                double b[4], aop[RB][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) aop[i][j] = bop[i][(s0 + j) * 64];
-                    b[j] = Kt[(4 * (s0 + j) + g) * PD + nl];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int i = 0; i < RB; ++i)
-                        if (ok[i]) acc[i][j & 1] = CBF_MFMA(aop[i][j], b[j], acc[i][j & 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < RB; ++i) a2[i] = acc[i][0] + acc[i][1];
-        }
+        wv.image_times_tile(wv.bop, Kt, a2);
 
         // ---- D': A2 of the whole block where every wave reads it, and as this column block's C-layout image (W_d)
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
-            if (ok[i]) {
-                double* own = A2t + 16 * rbs[i] * PD;
-                double* pi = a.a2img + (cb * NBLK + rbs[i]) * 256 + l;
+            if (wv.ok[i]) {
+                double* own = A2t + 16 * wv.rbs[i] * PD;
+                double* pi = a.a2img + (cb * NBLK + wv.rbs[i]) * 256 + l;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     own[(g + 4 * r) * PD + nl] = a2[i][r];
@@ -211,168 +141,53 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_bwd_kern
         for (int d = 0; d < Do; ++d) {
             const double* sop[RB];
 #pragma unroll
-            for (int i = 0; i < RB; ++i) sop[i] = a.Sp + (int64_t(d) * NBLK + rbs[i]) * KS * 64 + l;
-            d4 acc[RB][2];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) { acc[i][0] = d4{0, 0, 0, 0}; acc[i][1] = d4{0, 0, 0, 0}; }
-#pragma unroll 1
-            for (int s0 = 0; s0 < KSr; s0 += 4) {
-                double b[4], aop[RB][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) aop[i][j] = sop[i][(s0 + j) * 64];
-                    b[j] = A2t[(4 * (s0 + j) + g) * PD + nl];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int i = 0; i < RB; ++i)
-                        if (ok[i]) acc[i][j & 1] = CBF_MFMA(aop[i][j], b[j], acc[i][j & 1]);
-            }
+            for (int i = 0; i < RB; ++i) sop[i] = a.Sp + (int64_t(d) * NBLK + wv.rbs[i]) * WV::KS * 64 + l;
+            d4 sa[RB];
+            wv.image_times_tile(sop, A2t, sa);
             const double fvd = Fv[d * PD + nl];
 #pragma unroll
             for (int i = 0; i < RB; ++i)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) sq[i][r] = fma(acc[i][0][r] + acc[i][1][r], fvd, sq[i][r]);
+                for (int r = 0; r < 4; ++r) sq[i][r] = fma(sa[i][r], fvd, sq[i][r]);
         }
         __syncthreads();                                // every wave is done reading the A2 tile: phase E overwrites it
 
-        // ---- E: A2bar, and the parameter adjoints that contract over the 16 points
-        double fvsum = 0.0;
-        double fmB[4], fvB[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            fmB[s] = Fm[(4 * s + g) * PD + nl];
-            fvB[s] = Fv[(4 * s + g) * PD + nl];
-            fvsum += fvB[s];
-        }
-        fvsum += __shfl_xor(fvsum, 16);
-        fvsum += __shfl_xor(fvsum, 32);
-        if (w == 0 && g == 0) gsig += fvsum;            // d fvar / d sigma^2 = 1 (columns beyond npts hold zeros)
-        double fmT[4];                                  // the same tile with the point index as k: [n = 4s+g][col = nl]
-#pragma unroll
-        for (int s = 0; s < 4; ++s) fmT[s] = Fm[nl * PD + 4 * s + g];
+        // ---- E: A2bar with the S_d term, and the parameter adjoints that contract over the 16 points (no s2bar); the
+        // transposes and the Kinvbar step are the shared pieces, stash slot = column block
+        GpUpstream up;
+        wv.template load_upstream<false>(Fm, Fv, up, gsig);
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
-            if (ok[i]) {
-                const double* mBp = a.rk.muB + rbs[i] * 256 + l;
+            if (wv.ok[i]) {
+                const double* mBp = a.rk.muB + wv.rbs[i] * 256 + l;
                 double mv[4];
 #pragma unroll
                 for (int s = 0; s < 4; ++s) mv[s] = mBp[s * 64];
                 d4 T1 = {0, 0, 0, 0};
 #pragma unroll
-                for (int s = 0; s < 4; ++s) T1 = CBF_MFMA(mv[s], fmB[s], T1);
+                for (int s = 0; s < 4; ++s) T1 = CBF_MFMA(mv[s], up.fmB[s], T1);
                 d4 a2bar;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) a2bar[r] = T1[r] + 2.0 * sq[i][r] - kreg[i][r] * fvsum;
-                // 16x16 transposes through this wave's own rows of the A2bar tile (nobody else reads them before the
-                // next barrier): C-layout (row g+4r, col nl) -> A-operand layout (row nl, k = 4s+g)
+                for (int r = 0; r < 4; ++r) a2bar[r] = T1[r] + 2.0 * sq[i][r] - kreg[i][r] * up.fvsum;
                 double a2T[4], abT[4];
-                double* own = A2t + 16 * rbs[i] * PD;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) a2T[s] = own[nl * PD + 4 * s + g];     // (phase D' left A2 in these rows)
+                double* own = A2t + 16 * wv.rbs[i] * PD;
+                wv.load_a(own, a2T);                    // (phase D' left A2 in these rows)
                 __builtin_amdgcn_wave_barrier();
+                wv.store_c(own, a2bar);                 // stays: A2bar tile of phase F
 #pragma unroll
-                for (int r = 0; r < 4; ++r) own[(g + 4 * r) * PD + nl] = a2bar[r];      // stays: A2bar tile of phase F
-#pragma unroll
-                for (int s = 0; s < 4; ++s) gMu[i] = CBF_MFMA(a2T[s], fmT[s], gMu[i]);   // mubar[m][d] += A2[m][n] Fm[d][n]
+                for (int s = 0; s < 4; ++s) acc.gMu[i] = CBF_MFMA(a2T[s], up.fmT[s], acc.gMu[i]);   // mubar[m][d] += A2[m][n] Fm[d][n]
                 __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) abT[s] = own[nl * PD + 4 * s + g];
-                if constexpr (STASH) {
-                    // A2bar^T and K^T of this row block as the MFMA operand images of Kinvbar += A2bar K^T
-                    double* pa = a.stash_a + (cb * NBLK + rbs[i]) * 256 + l;
-                    double* pk = a.stash_k + (cb * NBLK + rbs[i]) * 256 + l;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        pa[s * 64] = abT[s];                                                 // A[row m][k = point]
-                        pk[s * 64] = Kt[(16 * rbs[i] + nl) * PD + 4 * s + g];                // B[k = point][col m]
-                    }
-                } else {
-#pragma unroll
-                    for (int c2 = 0; c2 < NCB; ++c2) {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-                            const double kT = Kt[(16 * c2 + nl) * PD + 4 * s + g];
-                            gB[i][c2] = CBF_MFMA(abT[s], kT, gB[i][c2]);        // Kinvbar[m'][m] += A2bar[m'][n] K[m][n]
-                        }
-                    }
-                }
+                wv.load_a(own, abT);
+                wv.template kinv_adjoint<STASH>(i, abT, Kt, cb, a.stash_a, a.stash_k, acc.gB[i]);
             }
         }
         __syncthreads();
 
         // ---- F: Kbar, Ebar, input adjoint partials, Zbar~
         d4 ebar[RB];
-        {
-            d4 acc[RB][2];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) { acc[i][0] = d4{0, 0, 0, 0}; acc[i][1] = d4{0, 0, 0, 0}; }
-#pragma unroll 1
-            for (int s0 = 0; s0 < KSr; s0 += 4) {
-                double b[4], aop[RB][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) aop[i][j] = bop[i][(s0 + j) * 64];
-                    b[j] = A2t[(4 * (s0 + j) + g) * PD + nl];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int i = 0; i < RB; ++i)
-                        if (ok[i]) acc[i][j & 1] = CBF_MFMA(aop[i][j], b[j], acc[i][j & 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double v = (acc[i][0][r] + acc[i][1][r] - a2[i][r] * fvsum) * kreg[i][r];
-                    ebar[i][r] = (ok[i] && 16 * rbs[i] + 4 * r + g < M) ? v : 0.0;
-                }
-        }
-        {
-            d4 xp[JB];
-#pragma unroll
-            for (int jb = 0; jb < JB; ++jb) xp[jb] = d4{0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                if (ok[i]) {
-                    const double* ZTp = a.rk.ZT + rbs[i] * JB * 256 + l;
-#pragma unroll
-                    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) xp[jb] = CBF_MFMA(ZTp[(jb * 4 + r) * 64], ebar[i][r], xp[jb]);   // rows j, k = m
-                }
-            }
-#pragma unroll
-            for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) part[w * PSL + (jb * 4 + r) * 64 + l] = xp[jb][r];
-        }
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            if (ok[i]) {
-                double ebT[4];
-                double* ownk = Kt + 16 * rbs[i] * PD;    // the K tile is dead behind the barrier that ends phase E
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ownk[(g + 4 * r) * PD + nl] = ebar[i][r];
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) ebT[s] = ownk[nl * PD + 4 * s + g];
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) {
-                    const int j = 16 * jb + nl;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        double xT = (j < 4 * DK) ? xq[j * PD + 4 * s + g] : 0.0;
-                        if (j == D) xT = 1.0;                                         // ones column: row sums of Ebar
-                        gZ[i][jb] = CBF_MFMA(ebT[s], xT, gZ[i][jb]);                  // Zbar~[m][j] += Ebar[m][n] x~[j][n]
-                    }
-                }
-            }
-        }
+        wv.kbar(A2t, a2, up.fvsum, ebar);
+        wv.ebar_of(ebar, kreg, M, ebar);
+        wv.phase_F_tail(a.rk.ZT, Kt, xq, part, ebar, D, acc.gZ);
         __syncthreads();
 
         // ---- G: input adjoint of this block's points
@@ -405,39 +220,9 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_bwd_kern
     // ---- write this workgroup's slab
     __syncthreads();
     double* slab = a.gpart + int64_t(blockIdx.x) * a.slab;
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        if (ok[i]) {
-            const int rb = rbs[i];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                slab[SL::gMu + rb * 256 + r * 64 + l] = gMu[i][r];
-                slab[SL::gS2 + rb * 256 + r * 64 + l] = 0.0;        // (no diagonal sigma_z^2 in the full form)
-                if constexpr (!STASH) {
-#pragma unroll
-                    for (int c2 = 0; c2 < NCB; ++c2) slab[SL::gB + (rb * NBLK + c2) * 256 + r * 64 + l] = gB[i][c2][r];
-                }
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) slab[SL::gZ + (rb * JB + jb) * 256 + r * 64 + l] = gZ[i][jb][r];
-            }
-        }
-    }
-    for (int i = tid; i < 192; i += NT) slab[SL::small + i] = 0.0;
+    wv.template write_slab<STASH>(slab, acc);
     __syncthreads();
-#pragma unroll
-    for (int k2 = 0; k2 < GPW; ++k2) {
-        const int gi = w + k2 * W;
-        double v = glx[k2];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (gi < NG && nl == 0) slab[SL::small + 32 + 4 * gi + g] = v;
-    }
-    const double s1 = block_sum(gsig, red, tid, NT);
-    const double s2 = block_sum(glogsig, red, tid, NT);
-    if (tid == 0) {
-        slab[SL::small + 96] = s1;
-        slab[SL::small + 97] = s2;
-    }
+    wv.template write_sums<STASH>(slab, glx, gsig, glogsig, red);
 }
 
 template <int NBLK, int DK>
@@ -492,38 +277,11 @@ struct GpFqFwdGeom {
     static_assert(LDS_DOUBLES <= 163840 / 8, "LDS budget");
 };
 
-// out[i] = (rows of the A-operand image behind aop[i]) x (the [16 NBLK][17] tile in LDS); four k-steps of loads together
-template <int RB>
-__device__ __forceinline__ void fq_image_times_tile(const double* const (&aop)[RB], const bool (&ok)[RB], const double* tile,
-                                                    int KSr, int g, int nl, d4 (&out)[RB])
-{
-    constexpr int PD = 17;
-    d4 acc[RB][2];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) { acc[i][0] = d4{0, 0, 0, 0}; acc[i][1] = d4{0, 0, 0, 0}; }
-#pragma unroll 1
-    for (int s0 = 0; s0 < KSr; s0 += 4) {
-        double b[4], av[RB][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int i = 0; i < RB; ++i) av[i][j] = aop[i][(s0 + j) * 64];
-            b[j] = tile[(4 * (s0 + j) + g) * PD + nl];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-                if (ok[i]) acc[i][j & 1] = CBF_MFMA(av[i][j], b[j], acc[i][j & 1]);
-    }
-#pragma unroll
-    for (int i = 0; i < RB; ++i) out[i] = acc[i][0] + acc[i][1];
-}
-
 template <int NBLK, int RB, int DK>
 __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_fwd_kernel(GpFqFwdArgs a)
 {
-    constexpr int W = (NBLK + RB - 1) / RB, NT = 64 * W, MP = 16 * NBLK, KS = MP / 4;
+    typedef GpWave<NBLK, RB, DK> WV;
+    constexpr int W = WV::W, NT = WV::NT, MP = WV::MP;
     constexpr int PD = 17;
 
     extern __shared__ double lds[];
@@ -534,25 +292,11 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_fwd_kern
 
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, nl = l & 15;
     const int M = a.M, D = a.D, Do = a.Do;
-    const int KSr = a.pk.KSr;
     const double sig2 = a.pk.scal[CBFSSM_SCAL_SIGMA2];
 
-    bool ok[RB];
-    int rbs[RB];
-    double Zreg[RB][DK], czr[RB][4];
-    const double *bop[RB], *wop[RB], *wtop[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        ok[i] = (w * RB + i) < NBLK;
-        rbs[i] = ok[i] ? (w * RB + i) : (NBLK - 1);
-#pragma unroll
-        for (int s = 0; s < DK; ++s) Zreg[i][s] = a.pk.Zp[(rbs[i] * DK + s) * 64 + l];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) czr[i][r] = a.pk.cz[16 * rbs[i] + 4 * r + g];
-        bop[i] = a.pk.Bp + rbs[i] * KS * 64 + l;
-        wop[i] = a.pk.Wp + rbs[i] * KS * 64 + l;
-        wtop[i] = a.pk.WTp + rbs[i] * KS * 64 + l;
-    }
+    WV wv;
+    wv.setup(a.pk, tid);
+    wv.setup_forms(a.pk);
 
     for (int64_t cb = blockIdx.x; cb < a.nblocks; cb += gridDim.x) {
         const int64_t p0 = cb * 16;
@@ -566,72 +310,23 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_fwd_kern
         }
         __syncthreads();
 
-        // ---- kernel tile (rows of this wave); rows m >= M are exactly zero
+        // ---- kernel tile (rows of this wave): the shared phase B
         d4 kreg[RB];
-        {
-            double bx[DK], xx = 0.0;
-#pragma unroll
-            for (int s = 0; s < DK; ++s) {
-                bx[s] = xq[(4 * s + g) * PD + nl];
-                xx = fma(bx[s], bx[s], xx);
-            }
-            xx += __shfl_xor(xx, 16);
-            xx += __shfl_xor(xx, 32);
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                kreg[i] = d4{0, 0, 0, 0};
-                if (ok[i]) {
-                    d4 e;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r] = czr[i][r] - 0.5 * xx;
-#pragma unroll
-                    for (int s = 0; s < DK; ++s) e = CBF_MFMA(Zreg[i][s], bx[s], e);
-                    e = tile_exp4(e);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        kreg[i][r] = (16 * rbs[i] + 4 * r + g < M) ? e[r] : 0.0;
-                        Kt[(16 * rbs[i] + 4 * r + g) * PD + nl] = kreg[i][r];
-                    }
-                }
-            }
-        }
+        wv.kernel_tile(xq, Kt, M, kreg);
         __syncthreads();
 
-        // ---- A2 of this wave's rows and this wave's part of sigma^2 - fvar0
+        // ---- A2 of this wave's rows and this wave's part of sigma^2 - fvar0 (the shared A2 step), A2 -> LDS
         d4 a2[RB];
-        double v0 = 0.0;
-        if (a.tri) {
-            d4 A[RB];
-            fq_image_times_tile<RB>(wop, ok, Kt, KSr, g, nl, A);
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                if (ok[i]) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v0 = fma(A[i][r], A[i][r], v0);
-                        A2t[(16 * rbs[i] + g + 4 * r) * PD + nl] = A[i][r];
-                    }
-                }
-            }
-            __syncthreads();
-            fq_image_times_tile<RB>(wtop, ok, A2t, KSr, g, nl, a2);
-            __syncthreads();                            // every wave has read A before A2 takes its place
-        } else {
-            fq_image_times_tile<RB>(bop, ok, Kt, KSr, g, nl, a2);
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v0 = fma(kreg[i][r], a2[i][r], v0);
-        }
+        double v0 = wv.a2_forms(a.tri, Kt, A2t, kreg, a2);
+        if (a.tri) __syncthreads();                     // every wave has read A before A2 takes its place
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
-            if (ok[i]) {
+            if (wv.ok[i]) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) A2t[(16 * rbs[i] + g + 4 * r) * PD + nl] = a2[i][r];
+                for (int r = 0; r < 4; ++r) A2t[(16 * wv.rbs[i] + g + 4 * r) * PD + nl] = a2[i][r];
             }
         }
-        v0 += __shfl_xor(v0, 16);
-        v0 += __shfl_xor(v0, 32);
+        v0 = gp_sum_groups(v0);
         if (g == 0) red[(w * 17 + 16) * 16 + nl] = v0;
         __syncthreads();
 
@@ -640,16 +335,15 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_fwd_kern
         for (int d = 0; d < Do; ++d) {
             const double* sop[RB];
 #pragma unroll
-            for (int i = 0; i < RB; ++i) sop[i] = a.Sp + (int64_t(d) * NBLK + rbs[i]) * KS * 64 + l;
+            for (int i = 0; i < RB; ++i) sop[i] = a.Sp + (int64_t(d) * NBLK + wv.rbs[i]) * WV::KS * 64 + l;
             d4 sa[RB];
-            fq_image_times_tile<RB>(sop, ok, A2t, KSr, g, nl, sa);
+            wv.image_times_tile(sop, A2t, sa);
             double v = 0.0;
 #pragma unroll
             for (int i = 0; i < RB; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v = fma(a2[i][r], sa[i][r], v);
-            v += __shfl_xor(v, 16);
-            v += __shfl_xor(v, 32);
+            v = gp_sum_groups(v);
             if (g == 0) red[(w * 17 + d) * 16 + nl] = v;
         }
 
@@ -657,7 +351,7 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_fullq_fwd_kern
         if (w == W - 1) {
             d4 fm[2] = {d4{0, 0, 0, 0}, d4{0, 0, 0, 0}};
 #pragma unroll 1
-            for (int s = 0; s < KSr; ++s) fm[s & 1] = CBF_MFMA(a.pk.muA[s * 64 + l], A2t[(4 * s + g) * PD + nl], fm[s & 1]);
+            for (int s = 0; s < wv.KSr; ++s) fm[s & 1] = CBF_MFMA(a.pk.muA[s * 64 + l], A2t[(4 * s + g) * PD + nl], fm[s & 1]);
             const int64_t p = p0 + nl;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

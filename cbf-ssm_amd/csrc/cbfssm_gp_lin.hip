@@ -5,12 +5,11 @@
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_lin.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPLIN_DECLARE)
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
 
 static int gp_lin_maxwg(int NBLK)
 {
@@ -30,18 +29,6 @@ static int dispatch_gp_lin(int NBLK, int DK, const GpLinArgs& a, unsigned nwg, h
 #undef X
     }
     return -3;
-}
-
-// the limits of cbfssm_gp_predict_f64, checked on the layout itself (as cbfssm_gp_predict_bwd_f64 does)
-static bool gp_lin_layout_ok(const cbfssm_pack_layout* L)
-{
-    if (!L) return false;
-    if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
-    if (gp_lin_maxwg(L->NBLK) == 0 || 16 * L->NBLK < L->M) return false;
-    if ((L->DK != 2 && L->DK != 4 && L->DK != 6) || 4 * L->DK < L->D) return false;
-    if (L->KS != 4 * L->NBLK) return false;
-    if (L->JB != (4 * L->DK + 1 + 15) / 16) return false;
-    return true;
 }
 
 // alpha[d][m] = (K^-1 mu)[m][d] for d < 16, m < 16 NBLK, zero in the padding.  One workgroup per output dimension.
@@ -93,7 +80,7 @@ extern "C" {
 
 int64_t cbfssm_gp_linearize_work_elems(const cbfssm_pack_layout* L)
 {
-    if (!gp_lin_layout_ok(L)) return -1;
+    if (!gp_layout_ok(L)) return -1;
     return int64_t(16) * 16 * L->NBLK;
 }
 
@@ -101,7 +88,7 @@ int cbfssm_gp_linearize_f64(const cbfssm_pack_layout* L, const double* pack, con
                             double* fvar, double* dmean, double* dvar, double* work, void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_lin_layout_ok(L))
+    if (!gp_layout_ok(L))
         return fail(-3, "gp_linearize limits: M <= %d, D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (npts < 0 || npts > (int64_t(1) << 34)) return fail(-1, "bad npts");
@@ -115,10 +102,7 @@ int cbfssm_gp_linearize_f64(const cbfssm_pack_layout* L, const double* pack, con
     if (e != hipSuccess) return fail(-int(e) - 1000, "gp_linearize: alpha launch failed");
     GpLinArgs a;
     memset(&a, 0, sizeof(a));
-    a.pk.Bp = pack + L->Bp; a.pk.Zp = pack + L->Zp; a.pk.cz = pack + L->cz; a.pk.muA = pack + L->muA;
-    a.pk.invl = pack + L->invl; a.pk.scal = pack + L->scal; a.pk.KSr = (L->M + 3) / 4;
-    a.pk.Wp = pack + L->Wp; a.pk.WTp = pack + L->WTp;
-    a.rk.muB = pack + L->muB; a.rk.s2B = pack + L->s2B; a.rk.ZT = pack + L->ZT;
+    gp_pack_ptrs(L, pack, a.pk, a.rk);
     a.X = X; a.alpha = work; a.fmean = fmean; a.fvar = fvar; a.dmean = dmean; a.dvar = dvar;
     a.npts = npts; a.nblocks = (npts + 15) / 16;
     a.M = L->M; a.D = L->D; a.Do = L->Do; a.tri = tri;

@@ -5,16 +5,11 @@
 #include <cstring>
 #include "../../include/cbfssm_hip.h"
 #include "cbfssm_gp_mm.hpp"
+#include "cbfssm_gp_host.hpp"
 
 CBF_FOR_EACH_GPBWD_NBLK(CBF_GPMM_DECLARE)
 
 namespace cbfssm {
-
-int fail(int rc, const char* fmt, ...);   // cbfssm_api.hip
-
-// cbfssm_gp_lin.hip
-__global__ void gp_lin_alpha_kernel(const double* Kinv, const double* G, const double* muB, int M, int Do, int MP, int tri,
-                                    double* alpha);
 
 static int gp_mm_maxwg(int NBLK)
 {
@@ -34,18 +29,6 @@ static int dispatch_gp_mm(int NBLK, int DK, const GpMmArgs& a, unsigned nwg, hip
 #undef X
     }
     return -3;
-}
-
-// the limits of cbfssm_gp_predict_f64, checked on the layout itself (as cbfssm_gp_linearize_f64 does)
-static bool gp_mm_layout_ok(const cbfssm_pack_layout* L)
-{
-    if (!L) return false;
-    if (L->M < 1 || L->M > CBFSSM_MAX_M || L->D < 1 || L->D > 24 || L->Do < 1 || L->Do > CBFSSM_MAX_DOUT) return false;
-    if (gp_mm_maxwg(L->NBLK) == 0 || 16 * L->NBLK < L->M) return false;
-    if ((L->DK != 2 && L->DK != 4 && L->DK != 6) || 4 * L->DK < L->D) return false;
-    if (L->KS != 4 * L->NBLK) return false;
-    if (L->JB != (4 * L->DK + 1 + 15) / 16) return false;
-    return true;
 }
 
 // One wave per 16 x 16 tile (ib, jb) and output dimension d of W_d = K^-1 - K^-1 diag(s2_d) K^-1, the product on the f64
@@ -84,7 +67,7 @@ extern "C" {
 
 int64_t cbfssm_gp_moment_match_work_elems(const cbfssm_pack_layout* L)
 {
-    if (!gp_mm_layout_ok(L)) return -1;
+    if (!gp_layout_ok(L)) return -1;
     return int64_t(16) * 16 * L->NBLK + int64_t(L->Do) * L->NBLK * L->NBLK * 256;
 }
 
@@ -93,7 +76,7 @@ int cbfssm_gp_moment_match_f64(const cbfssm_pack_layout* L, const double* pack, 
                                void* stream)
 {
     if (!L) return fail(-1, "null layout");
-    if (!gp_mm_layout_ok(L))
+    if (!gp_layout_ok(L))
         return fail(-3, "gp_moment_match limits: M <= %d, D <= 24, Do <= %d, and a layout of cbfssm_gp_pack_layout (M=%d D=%d Do=%d)",
                     CBFSSM_MAX_M, CBFSSM_MAX_DOUT, L->M, L->D, L->Do);
     if (npts < 0 || npts > (int64_t(1) << 34)) return fail(-1, "bad npts");

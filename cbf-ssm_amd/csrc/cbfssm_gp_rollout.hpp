@@ -20,8 +20,8 @@
 // the rows j >= Do leave as ga[t].  The parameter adjoints stay in VGPRs for the whole pass and leave once per
 // workgroup in the Slab<> layout; sum Fv per state dim goes to the slab's d/d var_x entries (d loss / d var_add).
 // Tile heights above seven row blocks write the stash operand images per (workgroup, step) slot.
-// (Phases B to F are a copy of the batch kernel's, not a shared body: the two differ in what loads the tiles, in the slot
-// index and in phase G, which sit at both ends of every step, and the batch kernel's code stays what it was.)
+// Phases B to F, the row-block setup and the slab write are the shared body of cbfssm_gp_tile.hpp (GpWave), the same calls
+// as in the batch kernel; what loads the tiles, the stash slot index, phase G and the carry are this kernel's own.
 // No atomics, one writer per output: two calls are bitwise identical.  Padded chains carry zero adjoints and the rows
 // m >= M of the tiles are zero, so both contribute exactly zero.
 #pragma once
@@ -216,13 +216,13 @@ struct GpRollBwdGeom {
 template <int NBLK, int RB, int DK, bool STASH>
 __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_rollout_bwd_kernel(GpRollBwdArgs a)
 {
-    constexpr int W = (NBLK + RB - 1) / RB, NT = 64 * W, MP = 16 * NBLK, KS = MP / 4;
-    constexpr int JB = (4 * DK + 1 + 15) / 16;
+    typedef GpWave<NBLK, RB, DK> WV;
+    constexpr int W = WV::W, NT = WV::NT, MP = WV::MP;
+    constexpr int JB = WV::JB;
     constexpr int NG = 4 * JB;                          // 4-row groups of the input-adjoint tile
     constexpr int GPW = (NG + W - 1) / W;               // groups per wave in phase G
     constexpr int PD = 17;
     constexpr int PSL = JB * 256;
-    typedef Slab<NBLK, JB, STASH> SL;
 
     extern __shared__ double lds[];
     double* xq = lds;                                   // [4 DK][17] scaled inputs x~[j][n]
@@ -237,39 +237,16 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_rollout_bwd_ke
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, nl = l & 15;
     const int M = a.M, D = a.D, Do = a.Do, N = a.N, T = a.T;
     const int Da = D - Do;
-    const int KSr = a.pk.KSr;
     const int dir = a.reverse ? -1 : 1;
     const int64_t p0 = int64_t(blockIdx.x) * 16;
     const double gent = a.g_ent[0];
 
-    bool ok[RB];
-    int rbs[RB];
-    double Zreg[RB][DK], czr[RB][4];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        ok[i] = (w * RB + i) < NBLK;
-        rbs[i] = ok[i] ? (w * RB + i) : (NBLK - 1);
-#pragma unroll
-        for (int s = 0; s < DK; ++s) Zreg[i][s] = a.pk.Zp[(rbs[i] * DK + s) * 64 + l];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) czr[i][r] = a.pk.cz[16 * rbs[i] + 4 * r + g];
-    }
-    const double* bop[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) bop[i] = a.pk.Bp + rbs[i] * KS * 64 + l;
+    WV wv;
+    wv.setup(a.pk, tid);
 
     // ---- accumulators of the parameter adjoints (all steps of this workgroup)
-    constexpr int NCB = STASH ? 1 : NBLK;
-    d4 gMu[RB], gS2[RB], gZ[RB][JB], gB[RB][NCB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        gMu[i] = d4{0, 0, 0, 0};
-        gS2[i] = d4{0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < JB; ++j) gZ[i][j] = d4{0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) gB[i][j] = d4{0, 0, 0, 0};
-    }
+    GpAdjAcc<NBLK, RB, JB, STASH> acc;
+    acc.zero();
     double glx[GPW];
 #pragma unroll
     for (int k2 = 0; k2 < GPW; ++k2) glx[k2] = 0.0;
@@ -315,211 +292,26 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_rollout_bwd_ke
         }
         __syncthreads();
 
-        // ---- B: kernel tile (rows of this wave); rows m >= M are exactly zero
+        // ---- B: kernel tile (rows of this wave)
         d4 kreg[RB];
-        {
-            double bx[DK], xx = 0.0;
-#pragma unroll
-            for (int s = 0; s < DK; ++s) {
-                bx[s] = xq[(4 * s + g) * PD + nl];
-                xx = fma(bx[s], bx[s], xx);
-            }
-            xx += __shfl_xor(xx, 16);
-            xx += __shfl_xor(xx, 32);
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                kreg[i] = d4{0, 0, 0, 0};
-                if (ok[i]) {
-                    d4 e;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r] = czr[i][r] - 0.5 * xx;
-#pragma unroll
-                    for (int s = 0; s < DK; ++s) e = CBF_MFMA(Zreg[i][s], bx[s], e);
-                    e = tile_exp4(e);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        kreg[i][r] = (16 * rbs[i] + 4 * r + g < M) ? e[r] : 0.0;
-                        Kt[(16 * rbs[i] + 4 * r + g) * PD + nl] = kreg[i][r];
-                    }
-                }
-            }
-        }
+        wv.kernel_tile(xq, Kt, M, kreg);
         __syncthreads();
 
         // ---- C: A2 rows of this wave (K^-1 streams from L2 as the A-operand image of the pack)
         d4 a2[RB];
-        {
-            d4 acc[RB][2];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) { acc[i][0] = d4{0, 0, 0, 0}; acc[i][1] = d4{0, 0, 0, 0}; }
-#pragma unroll 1
-            for (int s0 = 0; s0 < KSr; s0 += 4) {
-                double b[4], aop[RB][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) aop[i][j] = bop[i][(s0 + j) * 64];
-                    b[j] = Kt[(4 * (s0 + j) + g) * PD + nl];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int i = 0; i < RB; ++i)
-                        if (ok[i]) acc[i][j & 1] = CBF_MFMA(aop[i][j], b[j], acc[i][j & 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < RB; ++i) a2[i] = acc[i][0] + acc[i][1];
-        }
+        wv.image_times_tile(wv.bop, Kt, a2);
 
-        // ---- E: A2bar, and the parameter adjoints that contract over the 16 chains
-        double fvsum = 0.0;
-        double fmB[4], fvB[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            fmB[s] = Fm[(4 * s + g) * PD + nl];
-            fvB[s] = Fv[(4 * s + g) * PD + nl];
-            fvsum += fvB[s];
-        }
-        fvsum += __shfl_xor(fvsum, 16);
-        fvsum += __shfl_xor(fvsum, 32);
-        if (w == 0 && g == 0) gsig += fvsum;            // d fvar / d sigma^2 = 1 (padded chains hold zeros)
-        double fmT[4], fvT[4];                          // the same tiles with the chain index as k: [n = 4s+g][col = nl]
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            fmT[s] = Fm[nl * PD + 4 * s + g];
-            fvT[s] = Fv[nl * PD + 4 * s + g];
-        }
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            if (ok[i]) {
-                const double* mBp = a.rk.muB + rbs[i] * 256 + l;
-                const double* sBp = a.rk.s2B + rbs[i] * 256 + l;
-                double mv[4], sv[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) { mv[s] = mBp[s * 64]; sv[s] = sBp[s * 64]; }
-                d4 T1 = {0, 0, 0, 0}, T2 = {0, 0, 0, 0};
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    T1 = CBF_MFMA(mv[s], fmB[s], T1);
-                    T2 = CBF_MFMA(sv[s], fvB[s], T2);
-                }
-                d4 a2bar;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) a2bar[r] = T1[r] + 2.0 * a2[i][r] * T2[r] - kreg[i][r] * fvsum;
-                // 16x16 transposes through this wave's own rows of the A2bar tile (nobody else reads them before the
-                // next barrier): C-layout (row g+4r, col nl) -> A-operand layout (row nl, k = 4s+g)
-                double a2T[4], abT[4];
-                double* own = A2t + 16 * rbs[i] * PD;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) own[(g + 4 * r) * PD + nl] = a2[i][r];
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) a2T[s] = own[nl * PD + 4 * s + g];
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int r = 0; r < 4; ++r) own[(g + 4 * r) * PD + nl] = a2bar[r];      // stays: A2bar tile of phase F
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    gMu[i] = CBF_MFMA(a2T[s], fmT[s], gMu[i]);                  // mubar[m][d] += A2[m][n] Fm[d][n]
-                    gS2[i] = CBF_MFMA(a2T[s] * a2T[s], fvT[s], gS2[i]);         // s2bar[m][d] += A2[m][n]^2 Fv[d][n]
-                }
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) abT[s] = own[nl * PD + 4 * s + g];
-                if constexpr (STASH) {
-                    // A2bar^T and K^T of this row block as the MFMA operand images of Kinvbar += A2bar K^T
-                    const int64_t slot = int64_t(blockIdx.x) * T + sp;
-                    double* pa = a.stash_a + (slot * NBLK + rbs[i]) * 256 + l;
-                    double* pk = a.stash_k + (slot * NBLK + rbs[i]) * 256 + l;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        pa[s * 64] = abT[s];                                                 // A[row m][k = chain]
-                        pk[s * 64] = Kt[(16 * rbs[i] + nl) * PD + 4 * s + g];                // B[k = chain][col m]
-                    }
-                } else {
-#pragma unroll
-                    for (int c2 = 0; c2 < NCB; ++c2) {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-                            const double kT = Kt[(16 * c2 + nl) * PD + 4 * s + g];
-                            gB[i][c2] = CBF_MFMA(abT[s], kT, gB[i][c2]);        // Kinvbar[m'][m] += A2bar[m'][n] K[m][n]
-                        }
-                    }
-                }
-            }
-        }
+        // ---- E: A2bar, and the parameter adjoints that contract over the 16 chains; stash slot = workgroup * T + step
+        GpUpstream up;
+        wv.load_upstream(Fm, Fv, up, gsig);
+        wv.template phase_E<STASH>(a.rk, up, Kt, A2t, a2, kreg, int64_t(blockIdx.x) * T + sp, a.stash_a, a.stash_k, acc);
         __syncthreads();
 
         // ---- F: Kbar, Ebar, input adjoint partials, Zbar~
         d4 ebar[RB];
-        {
-            d4 acc[RB][2];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) { acc[i][0] = d4{0, 0, 0, 0}; acc[i][1] = d4{0, 0, 0, 0}; }
-#pragma unroll 1
-            for (int s0 = 0; s0 < KSr; s0 += 4) {
-                double b[4], aop[RB][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) aop[i][j] = bop[i][(s0 + j) * 64];
-                    b[j] = A2t[(4 * (s0 + j) + g) * PD + nl];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int i = 0; i < RB; ++i)
-                        if (ok[i]) acc[i][j & 1] = CBF_MFMA(aop[i][j], b[j], acc[i][j & 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double v = (acc[i][0][r] + acc[i][1][r] - a2[i][r] * fvsum) * kreg[i][r];
-                    ebar[i][r] = (ok[i] && 16 * rbs[i] + 4 * r + g < M) ? v : 0.0;
-                }
-        }
-        {
-            d4 xp[JB];
-#pragma unroll
-            for (int jb = 0; jb < JB; ++jb) xp[jb] = d4{0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                if (ok[i]) {
-                    const double* ZTp = a.rk.ZT + rbs[i] * JB * 256 + l;
-#pragma unroll
-                    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) xp[jb] = CBF_MFMA(ZTp[(jb * 4 + r) * 64], ebar[i][r], xp[jb]);   // rows j, k = m
-                }
-            }
-#pragma unroll
-            for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) part[w * PSL + (jb * 4 + r) * 64 + l] = xp[jb][r];
-        }
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            if (ok[i]) {
-                double ebT[4];
-                double* ownk = Kt + 16 * rbs[i] * PD;    // the K tile is dead behind the barrier that ends phase E
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ownk[(g + 4 * r) * PD + nl] = ebar[i][r];
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) ebT[s] = ownk[nl * PD + 4 * s + g];
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) {
-                    const int j = 16 * jb + nl;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        double xT = (j < 4 * DK) ? xq[j * PD + 4 * s + g] : 0.0;
-                        if (j == D) xT = 1.0;                                         // ones column: row sums of Ebar
-                        gZ[i][jb] = CBF_MFMA(ebT[s], xT, gZ[i][jb]);                  // Zbar~[m][j] += Ebar[m][n] x~[j][n]
-                    }
-                }
-            }
-        }
+        wv.kbar(A2t, a2, up.fvsum, ebar);
+        wv.ebar_of(ebar, kreg, M, ebar);
+        wv.phase_F_tail(a.rk.ZT, Kt, xq, part, ebar, D, acc.gZ);
         __syncthreads();
 
         // ---- G: input adjoint of this step: state rows -> carry (gh0 at the first forward step), the others -> ga[t]
@@ -560,46 +352,10 @@ __global__ __launch_bounds__(64 * ((NBLK + RB - 1) / RB)) void gp_rollout_bwd_ke
     // ---- write this workgroup's slab
     __syncthreads();
     double* slab = a.gpart + int64_t(blockIdx.x) * a.slab;
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        if (ok[i]) {
-            const int rb = rbs[i];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                slab[SL::gMu + rb * 256 + r * 64 + l] = gMu[i][r];
-                slab[SL::gS2 + rb * 256 + r * 64 + l] = gS2[i][r];
-                if constexpr (!STASH) {
-#pragma unroll
-                    for (int c2 = 0; c2 < NCB; ++c2) slab[SL::gB + (rb * NBLK + c2) * 256 + r * 64 + l] = gB[i][c2][r];
-                }
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) slab[SL::gZ + (rb * JB + jb) * 256 + r * 64 + l] = gZ[i][jb][r];
-            }
-        }
-    }
-    for (int i = tid; i < 192; i += NT) slab[SL::small + i] = 0.0;
-    part[tid] = gva;                                    // (W PSL >= NT doubles; the steps' readers of part are done)
-    __syncthreads();
-    if (tid < 16) {                                     // d loss / d var_add by state dim: the threads tid' = tid mod 16, in order
-        constexpr int NL = (NT < 256) ? NT : 256;       // threads that load Fm / Fv entries
-        double s = 0.0;
-        for (int k = tid; k < NL; k += 16) s += part[k];
-        slab[SL::small + tid] = s;
-    }
-#pragma unroll
-    for (int k2 = 0; k2 < GPW; ++k2) {
-        const int gi = w + k2 * W;
-        double v = glx[k2];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (gi < NG && nl == 0) slab[SL::small + 32 + 4 * gi + g] = v;
-    }
-    const double s1 = block_sum(gsig, red, tid, NT);
-    const double s2 = block_sum(glogsig, red, tid, NT);
-    if (tid == 0) {
-        slab[SL::small + 96] = s1;
-        slab[SL::small + 97] = s2;
-    }
+    wv.template write_slab<STASH>(slab, acc);
+    const double gv[1] = {gva};                         // d loss / d var_add by state dim
+    wv.template write_state_sums<STASH>(slab, part, gv);
+    wv.template write_sums<STASH>(slab, glx, gsig, glogsig, red);
 }
 
 // ---- launchers: K^-1 placement (registers up to seven row blocks, streamed above), two row blocks per wave from 13 row
