@@ -8,8 +8,9 @@ those Jacobians are for -- a mean and a full state covariance per chain through 
 observations -- as one launch; `gp_eks_eval` adds the Rauch-Tung-Striebel sweep behind it: smoothed and one-step predictive
 moments, the smoothed initial belief and the lag-one cross-covariances.  `gp_moment_match_eval`, evaluation only, gives the
 exact moments of the GP output under a Gaussian input -- mean, full output covariance, covariance with the input -- in one
-launch; `gp_adf_eval` runs the assumed-density filter over them -- `gp_ekf_eval`'s recursion with the exact moments in place
-of the linearisation -- as one launch for all steps, and `gp_ads_eval` the smoother behind it.
+launch, and `gp_moment_match` the same results with a grad_fn into the belief (mean, cov; the model is a constant of the
+call): one fused adjoint launch; `gp_adf_eval` runs the assumed-density filter over them -- `gp_ekf_eval`'s recursion with
+the exact moments in place of the linearisation -- as one launch for all steps, and `gp_ads_eval` the smoother behind it.
 
 The CBF-SSM loss:
 
@@ -699,6 +700,80 @@ def gp_moment_match_eval(pack, mean, cov, cross=True):
         _l.check(lib.cbfssm_gp_moment_match_f64(C.byref(lay), _ptr(pack.buf), _ptr(mean), _ptr(cov), n, _ptr(fmean), _ptr(fcov),
                                                 _ptr(xcov), _ptr(info), _ptr(work), _stream()), 'cbfssm_gp_moment_match_f64')
     return fmean, fcov, xcov, info.to(torch.int64)
+
+
+# The same results with a grad_fn into the inputs of the call:
+#
+#     fmean, fcov, xcov, info = gp_moment_match(pack, mean, cov, cross=True)
+#
+# The model is a constant: the pack's values at the forward call are what the backward differentiates (the context keeps a
+# copy of the pack, as _GpPredict does), and no parameter tensor receives a gradient.  The backward is one adjoint launch
+# behind the forward's two pre-kernels (cbfssm_gp_moment_match_bwd_f64), which recomputes the forward quantities; a result the
+# loss does not use arrives as None and goes down as a NULL cotangent, whose terms the kernel skips.
+
+class _GpMomentMatch(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, mean, cov, cross):
+        fmean, fcov, xcov, info = gp_moment_match_eval(pack, mean, cov, cross=cross)
+        ctx.set_materialize_grads(False)
+        ctx.layout, ctx.buf = pack.layout, (pack.buf.clone() if mean.shape[0] else None)
+        ctx.mean = mean.detach().contiguous()
+        ctx.cov = cov.detach().contiguous() if cov is not None else None
+        ctx.mark_non_differentiable(info)
+        if cross:
+            return fmean, fcov, xcov, info
+        return fmean, fcov, info
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gfmean, gfcov, *rest):
+        gxcov = rest[0] if len(rest) == 2 else None
+        lib = _l.load()
+        lay, mean, cov = ctx.layout, ctx.mean, ctx.cov
+        need = ctx.needs_input_grad
+        n, dev = mean.shape[0], mean.device
+        if gfmean is None and gfcov is None and gxcov is None:
+            return None, None, None, None
+        # NaN-filled, not uninitialised: the kernel writes every entry of both gradients and reads nothing of `work` that this
+        # call did not write, and the fill is a few percent of the launch at most -- so every call is a poisoned-buffer run
+        nan = float('nan')
+        gmean = torch.full_like(mean, nan)
+        gcov = torch.full_like(cov, nan) if cov is not None else None
+        if n:
+            gfmean = gfmean.contiguous() if gfmean is not None else None
+            gfcov = gfcov.contiguous() if gfcov is not None else None
+            gxcov = gxcov.contiguous() if gxcov is not None else None
+            nwork = int(lib.cbfssm_gp_moment_match_bwd_work_elems(C.byref(lay)))
+            if nwork < 1:
+                raise _l.CbfssmHipError('cbfssm_gp_moment_match_bwd_work_elems refused the layout')
+            work = torch.full((nwork,), nan, dtype=torch.float64, device=dev)
+            _l.check(lib.cbfssm_gp_moment_match_bwd_f64(C.byref(lay), _ptr(ctx.buf), _ptr(mean), _ptr(cov), n, _ptr(gfmean),
+                                                        _ptr(gfcov), _ptr(gxcov), _ptr(gmean), _ptr(gcov), None, _ptr(work),
+                                                        _stream()), 'cbfssm_gp_moment_match_bwd_f64')
+        return None, (gmean if need[1] else None), (gcov if cov is not None and need[2] else None), None
+
+
+def gp_moment_match(pack, mean, cov, cross=True):
+    """gp_moment_match_eval's results on a prepared pack, with a grad_fn on fmean, fcov and xcov into `mean` and `cov` when
+    grad is enabled and one of them requires it (else the evaluation call itself).  The values are bitwise those of the
+    evaluation call; info never carries a grad_fn.  The gradient for cov is that of the function of
+    tril(cov) + tril(cov, -1)^T: exactly zero above the diagonal, both symmetric contributions on a strictly lower entry;
+    cov=None has no gradient and the gradient for mean is then the input gradient of predict.  The model is a constant of
+    the call: no parameter tensor is connected to these results.  Where info[n] != 0 the rows of point n of both gradients
+    are NaN.  Once differentiable; float64."""
+    dev = pack.buf.device
+    mean = torch.as_tensor(mean, dtype=torch.float64, device=dev)
+    assert mean.dim() == 2 and mean.shape[1] == pack.D, 'mean (npts, D)'
+    if cov is not None:
+        cov = torch.as_tensor(cov, dtype=torch.float64, device=dev)
+        assert tuple(cov.shape) == (mean.shape[0], pack.D, pack.D), 'cov (npts, D, D)'
+    if not (torch.is_grad_enabled() and (mean.requires_grad or (cov is not None and cov.requires_grad))):
+        return gp_moment_match_eval(pack, mean, cov, cross=cross)
+    out = _GpMomentMatch.apply(pack, mean, cov, bool(cross))
+    if cross:
+        return out
+    return out[0], out[1], None, out[2]
 
 
 # ---- the extended Kalman filter over the transition of one sparse GP: a Gaussian belief per chain through time -------------

@@ -45,6 +45,7 @@ SYMBOLS = (
     'cbfssm_gp_eks_work_elems', 'cbfssm_gp_eks_f64',
     'cbfssm_gp_ekf_save_f64', 'cbfssm_gp_ekf_bwd_workgroups', 'cbfssm_gp_ekf_bwd_work_elems', 'cbfssm_gp_ekf_bwd_f64',
     'cbfssm_gp_moment_match_work_elems', 'cbfssm_gp_moment_match_f64',
+    'cbfssm_gp_moment_match_bwd_work_elems', 'cbfssm_gp_moment_match_bwd_f64',
     'cbfssm_gp_adf_work_elems', 'cbfssm_gp_adf_f64', 'cbfssm_gp_ads_f64',
 )
 
@@ -205,6 +206,9 @@ def load():
     lib.cbfssm_gp_moment_match_work_elems.restype = i64
     lib.cbfssm_gp_moment_match_work_elems.argtypes = [C.POINTER(PackLayout)]
     lib.cbfssm_gp_moment_match_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.cbfssm_gp_moment_match_bwd_work_elems.restype = i64
+    lib.cbfssm_gp_moment_match_bwd_work_elems.argtypes = [C.POINTER(PackLayout)]
+    lib.cbfssm_gp_moment_match_bwd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cbfssm_gp_ekf_work_elems.restype = i64
     lib.cbfssm_gp_ekf_work_elems.argtypes = [C.POINTER(PackLayout)]
     lib.cbfssm_gp_ekf_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 5

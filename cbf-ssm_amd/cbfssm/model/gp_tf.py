@@ -46,8 +46,11 @@ moments, the smoothed initial belief and, on request, the lag-one cross-covarian
 full output covariance Cov(f, f) and Cov(f, x) in closed form for the RBF kernel (the moment matching of PILCO and of the GP
 assumed-density filter), right where the belief is as wide as a lengthscale and a first-order model is not -- one launch,
 the (N, M, M) matrix of expected kernel products never reaches memory.  `GPModel.transition_moments(h, P, a)` is the
-Gaussian one-step prediction of the recurrence on top of it: m+, P+ and Cov(h, h+).  Both are evaluation only and for the
-diagonal q(z).
+Gaussian one-step prediction of the recurrence on top of it: m+, P+ and Cov(h, h+).  Both are for the diagonal q(z) and
+evaluation only by default; with `input_grads=True` their results carry a grad_fn into the belief -- `mean` and `cov`, or
+`h`, `P` and `a` -- through one fused adjoint launch (cbfssm.hip.autograd.gp_moment_match), so that an input sequence, a
+policy or an initial belief can be optimised through a propagated belief over the learned model.  The model is a constant of
+such a call: its five leaves receive no gradient from these results (the reference has no moment matching to differentiate).
 
 `GPModel.adf(m0, P0, a, y, var_x, var_y, cond)` is the recursion that primitive was written for: the assumed-density
 (moment-matching) Kalman filter, `ekf` with the exact moments in place of the linearisation at the mean, as one launch for
@@ -460,7 +463,7 @@ class GPModel:
         A = dmean[:, :, :Do] + torch.eye(Do, dtype=torch.float64, device=dev)
         return A, dmean[:, :, Do:].contiguous()
 
-    def moment_match(self, mean, cov, cross=True):
+    def moment_match(self, mean, cov, cross=True, input_grads=False):
         """An addition to the reference's surface: the exact moments of the GP output under a Gaussian input
         x[n] ~ N(mean[n], cov[n]) -- the moment matching of PILCO and of the GP assumed-density filter, closed form for the
         RBF kernel, where `linearize` is first order at the mean -- as one launch:
@@ -475,8 +478,18 @@ class GPModel:
         zero blocks, rank one and cov = 0 are ordinary inputs; cov = 0 gives `predict` back (diag fcov = fvar) and xcov
         exactly zero.  Returns (fmean, fcov, xcov, info); cross=False leaves xcov out (None; the other results are bitwise
         the same).  info (N) int64 is 0, or 1 / 2 where cov[n] is not positive semi-definite (a non-positive pivot in the
-        first / second factorisation): the results of that point are NaN and nothing else is affected.  Evaluation only:
-        the results carry no grad_fn whatever the leaves or the inputs ask for.  Raises ValueError on a q_full=True model."""
+        first / second factorisation): the results of that point are NaN and nothing else is affected.  Evaluation only by
+        default: the results carry no grad_fn whatever the leaves or the inputs ask for.
+
+        input_grads=True (named after loss_and_grads(..., input_grads=True)): when grad is enabled and `mean` or `cov`
+        requires it, fmean, fcov and xcov carry a grad_fn into them -- the same launch forward (bitwise the same values),
+        one fused adjoint launch backward, once differentiable; info never does.  The gradient for cov is that of the
+        function of tril(cov) + tril(cov, -1)^T: exactly zero above the diagonal, both symmetric contributions on a strictly
+        lower entry; cov=None has no gradient and the gradient for mean is then the input gradient of `predict`.  The model
+        is a constant of the call -- the values its leaves had at the call: the five leaves get no gradient from these
+        results whatever their requires_grad says (their .grad stays None, torch.autograd.grad(loss, leaf) fails as for any
+        unconnected tensor).  Where info[n] != 0 the rows of point n of both gradients are NaN.
+        Raises ValueError on a q_full=True model."""
         self._no_full_q('moment_match')
         from ..hip import autograd as _ag
         dev = self.zeta_pos.device
@@ -486,9 +499,11 @@ class GPModel:
             cov = _f64(cov, dev)
             assert tuple(cov.shape) == (mean.shape[0], self.in_dim, self.in_dim), 'cov (N, in_dim, in_dim)'
         pack = self._prepared() if mean.shape[0] else self._pack                 # (nothing runs without a point)
+        if input_grads:
+            return _ag.gp_moment_match(pack, mean, cov, cross=cross)
         return _ag.gp_moment_match_eval(pack, mean, cov, cross=cross)
 
-    def transition_moments(self, h, P, a=None):
+    def transition_moments(self, h, P, a=None, input_grads=False):
         """The Gaussian one-step prediction of the recurrence `rollout`, `filter` and `ekf` run, h+ = h + f(concat(h, a)),
         for a belief h ~ N(h[n], P[n]) and a known input a (input covariance blockdiag(P, 0)), by `moment_match`:
 
@@ -497,8 +512,10 @@ class GPModel:
 
         h (N, out_dim), P (N, out_dim, out_dim) of which only the lower triangle is read, a (N, in_dim - out_dim) or None
         when the GP takes the state alone.  Returns (m+, P+, cross, info); P+ is bitwise symmetric; the process noise var_x
-        is the caller's to add; info as in `moment_match`.  Evaluation only.  Raises ValueError on a q_full=True model and
-        when in_dim < out_dim."""
+        is the caller's to add; info as in `moment_match`.  Evaluation only by default; input_grads=True: m+, P+ and cross
+        carry a grad_fn into h, P (the gradient of the function of its lower triangle) and a when one of them requires it --
+        `moment_match(..., input_grads=True)` with the tensor-library steps around it on the tape; the model is a constant.
+        Raises ValueError on a q_full=True model and when in_dim < out_dim."""
         self._no_full_q('transition_moments')
         Do, Da = self.out_dim, self.in_dim - self.out_dim
         if Da < 0:
@@ -519,7 +536,7 @@ class GPModel:
             X = torch.cat([h, a], dim=1)
             S = torch.zeros(h.shape[0], self.in_dim, self.in_dim, dtype=torch.float64, device=dev)
             S[:, :Do, :Do] = Pl
-        fmean, fcov, xcov, info = self.moment_match(X, S)
+        fmean, fcov, xcov, info = self.moment_match(X, S, input_grads=input_grads)
         Cm = xcov[:, :, :Do].transpose(1, 2)                                     # Cov(h, f)
         low = torch.tril(P + Cm + Cm.transpose(1, 2) + fcov)
         Pn = low + torch.tril(low, -1).transpose(1, 2)

@@ -297,6 +297,34 @@ int cbfssm_gp_moment_match_f64(const cbfssm_pack_layout* layout, const double* p
                                int64_t npts, double* fmean, double* fcov, double* xcov, double* info, double* work, void* stream);
 
 /*
+ * The adjoint of cbfssm_gp_moment_match_f64 with respect to the INPUTS of the call, mean and cov; the model (the pack) is a
+ * constant.  What planning and policy search through a propagated belief over a fixed, learned model needs.
+ *
+ * cbfssm_gp_moment_match_bwd_f64: pack, mean, cov as in the forward call; gfmean (npts, Do), gfcov (npts, Do, Do), which need
+ *   not be symmetric, and gxcov (npts, Do, D): the cotangents of the three results, each NULL for a zero cotangent (its terms
+ *   are skipped; all three NULL: -1) -> gmean (npts, D), gcov (npts, D, D), which is NULL exactly when cov is, and, when the
+ *   pointer is not NULL, info (npts) as in the forward.  gcov is the gradient of the function of tril(cov) + tril(cov, -1)^T:
+ *   exactly zero above the diagonal (written by the kernel), and a strictly lower entry carries both symmetric contributions.
+ *   With cov NULL, gmean is the input gradient of predict.  Where info[n] != 0 the rows of point n of both gradients are NaN,
+ *   by select; no other point is affected.  The forward quantities are recomputed: no state of the forward call is needed.
+ *   The forward's two pre-kernels (alpha, the W_d tiles) run once per call into `work`
+ *   (cbfssm_gp_moment_match_bwd_work_elems doubles: the forward's sections and a scratch per workgroup behind them), then
+ *   ONE launch does the rest: per pair of points the forward's factorisations and tile walk, per tile
+ *   Qbar = alpha (gfcov + gfcov^T) / 2 alpha^T on the f64 MFMA units less sum_d gfcov_dd W_d, E = Qbar o Q, its row and
+ *   column sums and U^T E with the tile as the B operand; then substitutions with the two D x D factors.  No Cholesky
+ *   adjoint and no M x M cotangent in memory.
+ * No atomics, no allocation, no host synchronisation, every output entry has one writer, every sum over waves in a fixed
+ * order: two calls are bitwise identical and the gradient of a point does not depend on the other points of the call;
+ * nothing is launched at npts = 0.  Limits as cbfssm_gp_predict_f64 (M <= 320, D <= 24, Do <= 16), else -3 before any
+ * launch; NULL layout, pack, mean, gmean or work, no cotangent, gcov without cov or cov without gcov, or npts < 0: -1.  The
+ * count is host arithmetic in 64 bits and returns -1 for a bad layout.
+ */
+int64_t cbfssm_gp_moment_match_bwd_work_elems(const cbfssm_pack_layout* layout);  /* gp_tf.py:132-161 */
+int cbfssm_gp_moment_match_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* mean,  /* gp_tf.py:132-161 */
+                                   const double* cov, int64_t npts, const double* gfmean, const double* gfcov,
+                                   const double* gxcov, double* gmean, double* gcov, double* info, double* work, void* stream);
+
+/*
  * Assumed-density (moment-matching) Kalman filter over the transition of one sparse GP, and the Rauch-Tung-Striebel
  * smoother behind it: the recursion of cbfssm_gp_ekf_f64 with the exact moments of cbfssm_gp_moment_match_f64 in place of
  * the linearisation at the mean (GP-ADF).  Per chain n and step t, with x = concat(m, a[t]) and S = blockdiag(P, 0):
