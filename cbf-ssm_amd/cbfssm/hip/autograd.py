@@ -1029,6 +1029,89 @@ def gp_ads_eval(pack, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):
     return EksResult(smeans, scovs, loglik, means, covs, pmeans, pcovs, sm_init, sP_init, lag1, info.to(torch.int64))
 
 
+# The same filter with a grad_fn into the inputs of the call:
+#
+#     AdfResult = gp_adf(pack, m0, P0, a, y, var_x, var_y, cond=None)
+#
+# means, covs and loglik carry a grad_fn into m0, P0, a, y, var_x and var_y; pmeans, pcovs, cross and info do not.  The model
+# is a constant, as in gp_moment_match: the context keeps a copy of the pack and no parameter tensor receives a gradient.  The
+# forward is gp_adf_eval itself and saves nothing new (its records are its results); the backward is the two pre-kernels, ONE
+# reverse-time launch and the fixed-order sum of the variance partials (cbfssm_gp_adf_bwd_f64).  Conventions: gp_ekf's (P0's
+# lower triangle, None arguments, y and var_y under the mask, NULL cotangents).  Where info[n] != 0 the rows of chain n of the
+# gradients for m0, P0, a and y are NaN and so are those for var_x and var_y; no other chain's rows are affected.
+
+class _GpAdf(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, cond, m0, P0, a, y, var_x, var_y):
+        with torch.no_grad():
+            m0d, P0d, ad, yd, vxd, vyd, cd, T, N, Dy = _adf_inputs('gp_adf', pack, m0, P0, a, y, var_x, var_y, cond)
+        res = gp_adf_eval(pack, m0d, P0d, ad, yd, vxd, vyd, cond=cd)
+        ctx.set_materialize_grads(False)                # an unused result reaches backward as None, and the entry point as NULL
+        ctx.empty = (N == 0 or T == 0)
+        ctx.layout, ctx.buf = pack.layout, (None if ctx.empty else pack.buf.clone())
+        ctx.has = (P0d is not None, ad is not None, vxd is not None, cd is not None)
+        ctx.dims = (T, N, Dy)
+        ctx.save_for_backward(m0d, yd, vyd, res.means, res.covs, res.pmeans, res.pcovs, res.info.to(torch.float64),
+                              *[t for t in (P0d, ad, vxd, cd) if t is not None])
+        ctx.mark_non_differentiable(res.pmeans, res.pcovs, res.cross, res.info)
+        return tuple(res)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gmeans, gcovs, gloglik, *rest):
+        lib = _l.load()
+        lay = ctx.layout
+        need = ctx.needs_input_grad                     # 2 m0, 3 P0, 4 a, 5 y, 6 var_x, 7 var_y
+        T, N, Dy = ctx.dims
+        hasP, hasa, hasvx, hascond = ctx.has
+        if gmeans is None and gcovs is None and gloglik is None:
+            return (None,) * 8
+        m0, y, var_y, means, covs, pmeans, pcovs, info = ctx.saved_tensors[:8]
+        more = list(ctx.saved_tensors[8:])
+        P0 = more.pop(0) if hasP else None
+        a = more.pop(0) if hasa else None
+        var_x = more.pop(0) if hasvx else None
+        cond = more.pop(0) if hascond else None
+        dev, Do = y.device, lay.Do
+        # NaN-filled, not uninitialised, as in _GpMomentMatch.backward: the launch writes every entry of the gradients and
+        # reads nothing of `work` that this call did not write, so every call is a poisoned-buffer run
+        nan = 0.0 if ctx.empty else float('nan')        # (no chain or no step: nothing is launched, the gradients are zero)
+        full = lambda *s: torch.full(s, nan, dtype=torch.float64, device=dev)
+        gm0, gy, gvy = torch.full_like(m0, nan), torch.full_like(y, nan), full(Dy)
+        gP0 = torch.full_like(P0, nan) if hasP else None
+        ga = torch.full_like(a, nan) if hasa else None
+        gvx = full(Do) if hasvx else None
+        if not ctx.empty:
+            con = lambda t: t.contiguous() if t is not None else None
+            gmeans, gcovs, gloglik = con(gmeans), con(gcovs), con(gloglik)
+            nwork = int(lib.cbfssm_gp_adf_bwd_work_elems(C.byref(lay), N))
+            if nwork < 1:
+                raise _l.CbfssmHipError('cbfssm_gp_adf_bwd_work_elems refused the layout')
+            work = full(nwork)
+            _l.check(lib.cbfssm_gp_adf_bwd_f64(C.byref(lay), _ptr(ctx.buf), _ptr(m0), _ptr(P0), _ptr(a), _ptr(y), _ptr(cond),
+                                               _ptr(var_x), _ptr(var_y), Dy, _ptr(means), _ptr(covs), _ptr(pmeans),
+                                               _ptr(pcovs), _ptr(info), _ptr(gmeans), _ptr(gcovs), _ptr(gloglik), N, T,
+                                               _ptr(gm0), _ptr(gP0), _ptr(ga), _ptr(gy), _ptr(gvx), _ptr(gvy), _ptr(work),
+                                               _stream()), 'cbfssm_gp_adf_bwd_f64')
+        return (None, None, gm0 if need[2] else None, gP0 if need[3] else None, ga if need[4] else None,
+                gy if need[5] else None, gvx if need[6] else None, gvy if need[7] else None)
+
+
+def gp_adf(pack, m0, P0, a, y, var_x, var_y, cond=None):
+    """gp_adf_eval's AdfResult on a prepared pack, with a grad_fn on means, covs and loglik into m0, P0, a, y, var_x and var_y
+    when grad is enabled and one of them requires it (else the evaluation call itself).  The seven results are bitwise those
+    of the evaluation call; pmeans, pcovs, cross and info never carry a grad_fn.  The model is a constant of the call: no
+    parameter tensor is connected to these results.  The gradient conventions stand above _GpAdf.  Once differentiable;
+    float64; no host synchronisation."""
+    dev = pack.buf.device
+    f64 = lambda t: torch.as_tensor(t, dtype=torch.float64, device=dev) if t is not None else None
+    m0, P0, a, y, var_x, var_y = (f64(t) for t in (m0, P0, a, y, var_x, var_y))
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (m0, P0, a, y, var_x, var_y))):
+        return gp_adf_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond)
+    return AdfResult(*_GpAdf.apply(pack, cond, m0, P0, a, y, var_x, var_y))
+
+
 # ---- the differentiable form of gp_ekf_eval: the marginal likelihood of a GP state-space model as a training objective ---
 #
 #     means, covs, loglik = gp_ekf(pack, m0, P0, a, y, var_x, var_y, zeta_pos, zeta_mean, zeta_var_unc, variance_unc,

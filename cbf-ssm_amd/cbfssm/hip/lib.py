@@ -47,6 +47,7 @@ SYMBOLS = (
     'cbfssm_gp_moment_match_work_elems', 'cbfssm_gp_moment_match_f64',
     'cbfssm_gp_moment_match_bwd_work_elems', 'cbfssm_gp_moment_match_bwd_f64',
     'cbfssm_gp_adf_work_elems', 'cbfssm_gp_adf_f64', 'cbfssm_gp_ads_f64',
+    'cbfssm_gp_adf_bwd_work_elems', 'cbfssm_gp_adf_bwd_f64',
 )
 
 
@@ -219,6 +220,9 @@ def load():
     lib.cbfssm_gp_adf_work_elems.argtypes = [C.POINTER(PackLayout)]
     lib.cbfssm_gp_adf_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 9
     lib.cbfssm_gp_ads_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 14
+    lib.cbfssm_gp_adf_bwd_work_elems.restype = i64
+    lib.cbfssm_gp_adf_bwd_work_elems.argtypes = [C.POINTER(PackLayout), i64]
+    lib.cbfssm_gp_adf_bwd_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip] + [vp] * 8 + [i64, i64] + [vp] * 8
     lib.cbfssm_gp_ekf_save_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 9
     lib.cbfssm_gp_ekf_bwd_workgroups.restype = i64
     lib.cbfssm_gp_ekf_bwd_workgroups.argtypes = [C.POINTER(PackLayout), i64]

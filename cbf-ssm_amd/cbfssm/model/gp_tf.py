@@ -56,7 +56,11 @@ such a call: its five leaves receive no gradient from these results (the referen
 (moment-matching) Kalman filter, `ekf` with the exact moments in place of the linearisation at the mean, as one launch for
 all steps -- the moment-match work of a step inside the time loop, alpha and the W_d tiles formed once per call.
 `GPModel.ads(...)` is the Rauch-Tung-Striebel smoother behind it (`eks`'s sweep on Cov(h_t, h_{t-1}) = P + Cx).  Both are
-evaluation only and for the diagonal q(z).
+for the diagonal q(z); `ads` is evaluation only, and so is `adf` by default.  `adf(..., input_grads=True)` gives means, covs
+and loglik a grad_fn into m0, P0, a, y, var_x and var_y -- one fused reverse-time adjoint launch over the whole propagated
+belief (cbfssm.hip.autograd.gp_adf), the model a constant of the call as for `moment_match`: an open-loop input sequence
+under an expected cost (cond = 0), an initial belief, or the noise levels by the ADF marginal likelihood -loglik.sum() become
+one-call objectives on the device.
 """
 import ctypes as C
 import numpy as np
@@ -542,7 +546,7 @@ class GPModel:
         Pn = low + torch.tril(low, -1).transpose(1, 2)
         return h + fmean, Pn, P + Cm, info
 
-    def adf(self, m0, P0, a, y, var_x, var_y, cond=None):
+    def adf(self, m0, P0, a, y, var_x, var_y, cond=None, input_grads=False):
         """The assumed-density (moment-matching) Kalman filter over this GP -- GP-ADF, PILCO's propagation: `ekf`'s
         recursion with the linearisation at the mean replaced by the exact moments of `moment_match` under the belief,
         which is what a belief as wide as a lengthscale needs.  One launch for all steps, per chain n:
@@ -570,13 +574,26 @@ class GPModel:
         semi-definite belief keeps it above (1 for I + S~, 1/2 for I/2 + S~: this flags a negative definite P0 whose two
         factors exist) -- possible only when P0 is not positive semi-definite: from that step on that chain's results and its loglik are NaN, and no other chain is affected.
         Two calls give bitwise-identical results, and a chain's results do not depend on the other chains of the call.  No
-        host synchronisation; nothing is launched without a chain or a step.  Evaluation only, float64, diagonal q(z),
-        forward in time: the results carry no grad_fn whatever the leaves or the inputs ask for.  Raises ValueError on a
-        q_full=True model and when in_dim < out_dim."""
+        host synchronisation; nothing is launched without a chain or a step.  Float64, diagonal q(z), forward in time.
+        Evaluation only by default: the results carry no grad_fn whatever the leaves or the inputs ask for.
+
+        input_grads=True (named as on `moment_match`): when grad is enabled and one of m0, P0, a, y, var_x, var_y requires
+        it, means, covs and loglik carry a grad_fn into those six -- the same launch forward (bitwise the same seven
+        results), one fused reverse-time adjoint launch backward, once differentiable; pmeans, pcovs, cross and info never
+        do.  The model is a constant of the call -- the values its leaves had at the call: the five leaves get no gradient
+        from these results whatever their requires_grad says.  The conventions are `ekf`'s: the gradient for P0 is that of
+        the function of tril(P0) + tril(P0, -1)^T (exactly zero above the diagonal, both contributions on a strictly lower
+        entry); an argument given as None has no gradient; the gradient for y is exactly 0 where cond = 0 (y may be NaN
+        there), and with cond = 0 everywhere those for y and var_y are zero tensors; cond gets none; the cotangent for covs
+        need not be symmetric; a result the loss does not use costs nothing.  Where info[n] != 0 the rows of chain n of the
+        gradients for m0, P0, a and y are NaN, those for var_x and var_y are NaN (the loss itself is), and the rows of every
+        other chain are unaffected.  Raises ValueError on a q_full=True model and when in_dim < out_dim."""
         self._no_full_q('adf')
         from ..hip import autograd as _ag
         y = _f64(y, self.zeta_pos.device)
         pack = self._prepared() if y.shape[0] * y.shape[1] else self._pack       # (nothing runs without a chain or a step)
+        if input_grads:
+            return _ag.gp_adf(pack, m0, P0, a, y, var_x, var_y, cond=cond)
         return _ag.gp_adf_eval(pack, m0, P0, a, y, var_x, var_y, cond=cond)
 
     def ads(self, m0, P0, a, y, var_x, var_y, cond=None, lag_one=False):

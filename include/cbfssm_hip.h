@@ -362,6 +362,40 @@ int cbfssm_gp_ads_f64(const cbfssm_pack_layout* layout, const double* pack, cons
                       double* lag1, double* info, double* work, void* stream);
 
 /*
+ * The adjoint of cbfssm_gp_adf_f64 with respect to the INPUTS of the call -- m0, P0, a, y, var_x, var_y; the model (the pack)
+ * is a constant -- from the cotangents of means, covs and loglik: what optimising an input sequence, an initial belief or
+ * the noise levels through a propagated belief over a fixed, learned model needs.
+ *
+ * cbfssm_gp_adf_bwd_f64: the inputs of the forward call; means, covs, pmeans, pcovs, info as cbfssm_gp_adf_f64 left them (the
+ *   forward saves nothing else: the moments of the GP are recomputed); gmeans (T, N, Do), gcovs (T, N, Do, Do), which need
+ *   not be symmetric, gloglik (N), each NULL where the loss does not use the result -> gm0 (N, Do), gP0 (N, Do, Do), ga
+ *   (T, N, D - Do), gy (T, N, Dy), gvar_x (Do), gvar_y (Dy).  gP0 is the gradient of the function of tril(P0) + tril(P0, -1)^T:
+ *   exactly zero above the diagonal (written here), both symmetric contributions on a strictly lower entry; gP0 is NULL
+ *   exactly when P0 is, gvar_x exactly when var_x is, ga only when D == Do.  gy is exactly 0 where cond = 0 (a select: y may
+ *   be NaN there); cond = 0 everywhere gives zero gy and gvar_y.  Where info[n] != 0 the rows of chain n of gm0, gP0, ga and
+ *   gy are NaN, by select, gvar_x and gvar_y are NaN, and the rows of every other chain are unaffected.  On one stream: the
+ *   forward's two pre-kernels once per call, ONE launch for all steps in reverse time (one workgroup per 16 chains: the
+ *   adjoint of the scalar updates and of the transition on the VALU, then the per-pair body of
+ *   cbfssm_gp_moment_match_bwd_f64's kernel on the step's staged problem), and a small launch that adds the workgroups'
+ *   var_x / var_y sums in the order of the workgroups.  `work`: cbfssm_gp_adf_bwd_work_elems(layout, N) doubles -- the
+ *   forward's sections and a block per workgroup of the launch, ceil(N / 16) of them; nothing of it is read that the call
+ *   did not write.  No atomics, no allocation, no host synchronisation; two calls are bitwise identical and a chain's rows
+ *   do not depend on the other chains of the call; nothing is launched and nothing written at N = 0 or T = 0.
+ *
+ * Limits and refusals as cbfssm_gp_adf_f64, the limits first, before any pointer is looked at: -3; NULL layout, pack, m0, y,
+ * var_y, a record, gm0, gy, gvar_y or work, NULL a or ga with D > Do, all three cotangents NULL, gP0 without P0 or P0 without
+ * gP0, the same for gvar_x and var_x, or N, T, Dy < 0: -1.  The count is host arithmetic in 64 bits and returns -1 for a bad
+ * layout or N < 0.
+ */
+int64_t cbfssm_gp_adf_bwd_work_elems(const cbfssm_pack_layout* layout, int64_t N);  /* gp_tf.py:132-161, cbfssm.py:199-221 */
+int cbfssm_gp_adf_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* m0, const double* P0,
+                          const double* a, const double* y, const double* cond, const double* var_x, const double* var_y,
+                          int Dy, const double* means, const double* covs, const double* pmeans, const double* pcovs,
+                          const double* info, const double* gmeans, const double* gcovs, const double* gloglik, int64_t N,
+                          int64_t T, double* gm0, double* gP0, double* ga, double* gy, double* gvar_x, double* gvar_y,
+                          double* work, void* stream);
+
+/*
  * ---- extended Kalman filter over the transition of ONE sparse GP: a Gaussian belief (m, P) per chain, carried through
  * time by the local linear model above inside the recurrence of CBF-SSM (cbfssm/model/cbfssm.py:199-221) and conditioned
  * on observations of the first Dy state dimensions (cbfssm.py:245-251), y = x[:Dy] + N(0, diag(var_y)).  Forward in time,
