@@ -776,6 +776,117 @@ def gp_moment_match(pack, mean, cov, cross=True):
     return out[0], out[1], None, out[2]
 
 
+# ... and with a grad_fn into the MODEL as well, the five tensors of GP_PARAM_NAMES:
+#
+#     fmean, fcov, xcov, info = gp_moment_match_params(pack, mean, cov, zeta_pos, zeta_mean, zeta_var_unc, variance_unc,
+#                                                      lengthscales_unc, cross=True)
+#
+# Forward: the pack is prepared from the leaves, then the evaluation launch (bitwise its values).  Backward: the input
+# adjoint launch (cbfssm_gp_moment_match_bwd_f64: gmean, gcov -- bitwise those of gp_moment_match), then, when a leaf wants
+# a gradient, cbfssm_gp_moment_match_params_bwd_f64 (one reduced slab; it contracts gmean and gcov with the inputs for the
+# belief's side of the lengthscale adjoint) and cbfssm_gp_tail_f64 with kl_weight 0.  The context keeps pack.buf.clone(),
+# pflat and cflat, as _GpEkf does.  Every buffer of the backward is filled with NaN before the launches: the kernels read
+# nothing they did not write.
+
+class _GpMomentMatchParams(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, pack, cross, mean, cov, *params):
+        pflat, cflat = _gp_flat(params)
+        n = mean.shape[0]
+        ctx.set_materialize_grads(False)
+        ctx.pflat, ctx.cflat = pflat, cflat
+        ctx.shapes = tuple(tuple(p.shape) for p in params)
+        ctx.mean = mean.detach().contiguous()
+        ctx.cov = cov.detach().contiguous() if cov is not None else None
+        if n:                                           # (without a point nothing is prepared or launched)
+            _gp_prepare(pack, params, cflat)
+        fmean, fcov, xcov, info = gp_moment_match_eval(pack, ctx.mean, ctx.cov, cross=cross)
+        ctx.layout, ctx.buf = pack.layout, (pack.buf.clone() if n else None)
+        ctx.mark_non_differentiable(info)
+        if cross:
+            ctx.save_for_backward(xcov)                 # (an output: the lengthscales scale it)
+            return fmean, fcov, xcov, info
+        return fmean, fcov, info
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gfmean, gfcov, *rest):
+        gxcov = rest[0] if len(rest) == 2 else None
+        lib = _l.load()
+        lay, mean, cov = ctx.layout, ctx.mean, ctx.cov
+        need = ctx.needs_input_grad                     # 2 mean, 3 cov, 4.. the leaves
+        n, dev = mean.shape[0], mean.device
+        if gfmean is None and gfcov is None and gxcov is None:
+            return (None,) * 9
+        nan = float('nan')
+        if n == 0:
+            gp = _gp_split(torch.zeros_like(ctx.pflat), ctx.shapes, need[4:])
+            return (None, None, torch.zeros_like(mean) if need[2] else None,
+                    torch.zeros_like(cov) if cov is not None and need[3] else None) + gp
+        gmean = torch.full_like(mean, nan)
+        gcov = torch.full_like(cov, nan) if cov is not None else None
+        gfmean = gfmean.contiguous() if gfmean is not None else None
+        gfcov = gfcov.contiguous() if gfcov is not None else None
+        gxcov = gxcov.contiguous() if gxcov is not None else None
+        nwork = int(lib.cbfssm_gp_moment_match_bwd_work_elems(C.byref(lay)))
+        if nwork < 1:
+            raise _l.CbfssmHipError('cbfssm_gp_moment_match_bwd_work_elems refused the layout')
+        work = torch.full((nwork,), nan, dtype=torch.float64, device=dev)
+        _l.check(lib.cbfssm_gp_moment_match_bwd_f64(C.byref(lay), _ptr(ctx.buf), _ptr(mean), _ptr(cov), n, _ptr(gfmean),
+                                                    _ptr(gfcov), _ptr(gxcov), _ptr(gmean), _ptr(gcov), None, _ptr(work),
+                                                    _stream()), 'cbfssm_gp_moment_match_bwd_f64')
+        gp = (None,) * 5
+        if any(need[4:]):
+            xcov = ctx.saved_tensors[0] if ctx.saved_tensors else None
+            nwork = int(lib.cbfssm_gp_moment_match_params_bwd_work_elems(C.byref(lay), n))
+            ntail = int(lib.cbfssm_train_tail_half_work_elems(C.byref(lay)))
+            if nwork < 1 or ntail < 1:
+                raise _l.CbfssmHipError('cbfssm_gp_moment_match_params_bwd_work_elems refused the layout')
+            work = torch.full((nwork,), nan, dtype=torch.float64, device=dev)
+            red = torch.full((lay.rev_slab,), nan, dtype=torch.float64, device=dev)
+            dense = torch.full((lay.M * lay.M,), nan, dtype=torch.float64, device=dev) if lay.rev_stash else None
+            _l.check(lib.cbfssm_gp_moment_match_params_bwd_f64(C.byref(lay), _ptr(ctx.buf), _ptr(ctx.cflat), _ptr(mean),
+                                                               _ptr(cov), n, _ptr(gfmean), _ptr(gfcov), _ptr(gxcov),
+                                                               _ptr(gmean), _ptr(gcov), _ptr(xcov), _ptr(red), _ptr(dense),
+                                                               _ptr(work), _stream()), 'cbfssm_gp_moment_match_params_bwd_f64')
+            twork = torch.full((ntail,), nan, dtype=torch.float64, device=dev)
+            gflat = torch.full_like(ctx.pflat, nan)
+            _l.check(lib.cbfssm_gp_tail_f64(C.byref(lay), _ptr(ctx.buf), _ptr(red), _ptr(dense), lay.M if lay.rev_stash else 0,
+                                            0.0, _ptr(ctx.pflat), _ptr(ctx.cflat), _ptr(twork), _ptr(gflat), _stream()),
+                     'cbfssm_gp_tail_f64')
+            gp = _gp_split(gflat, ctx.shapes, need[4:])
+        return (None, None, gmean if need[2] else None, gcov if cov is not None and need[3] else None) + gp
+
+
+def gp_moment_match_params(pack, mean, cov, *params, cross=True):
+    """gp_moment_match's results with a grad_fn into `mean`, `cov` AND the five parameter tensors (_gp_args' order) when grad
+    is enabled and one of them requires it: the pack is prepared from the parameters, the values are bitwise those of
+    gp_moment_match_eval on that pack, info never carries a grad_fn.  Otherwise the pack is prepared and the evaluation call
+    runs.  Conventions of gp_moment_match: the gradient for cov is that of the function of its lower triangle, a result the
+    loss does not use goes down as a NULL cotangent (none used: nothing is launched), cov=None is allowed (the leaf
+    gradients are then those of gp_predict for gmean = gfmean, gvar = diag gfcov), without a point nothing is prepared or
+    launched and the leaf gradients are zeros.  Where info[n] != 0 the rows of point n of the gradients for mean and cov
+    are NaN and so are all five leaf gradients, by select.  Once differentiable; float64; diagonal q(z); no host
+    synchronisation."""
+    dev = pack.buf.device
+    mean = torch.as_tensor(mean, dtype=torch.float64, device=dev)
+    assert mean.dim() == 2 and mean.shape[1] == pack.D, 'mean (npts, D)'
+    if cov is not None:
+        cov = torch.as_tensor(cov, dtype=torch.float64, device=dev)
+        assert tuple(cov.shape) == (mean.shape[0], pack.D, pack.D), 'cov (npts, D, D)'
+    params = _gp_args(pack, params)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [mean, cov] + params)):
+        if mean.shape[0]:
+            pflat, cflat = _gp_flat(params)
+            _gp_prepare(pack, params, cflat)
+        return gp_moment_match_eval(pack, mean, cov, cross=cross)
+    out = _GpMomentMatchParams.apply(pack, bool(cross), mean, cov, *params)
+    if cross:
+        return out
+    return out[0], out[1], None, out[2]
+
+
 # ---- the extended Kalman filter over the transition of one sparse GP: a Gaussian belief per chain through time -------------
 #
 #     means, covs, loglik = gp_ekf_eval(pack, m0, P0, a, y, var_x, var_y, cond=None)

@@ -46,6 +46,7 @@ SYMBOLS = (
     'cbfssm_gp_ekf_save_f64', 'cbfssm_gp_ekf_bwd_workgroups', 'cbfssm_gp_ekf_bwd_work_elems', 'cbfssm_gp_ekf_bwd_f64',
     'cbfssm_gp_moment_match_work_elems', 'cbfssm_gp_moment_match_f64',
     'cbfssm_gp_moment_match_bwd_work_elems', 'cbfssm_gp_moment_match_bwd_f64',
+    'cbfssm_gp_moment_match_params_bwd_work_elems', 'cbfssm_gp_moment_match_params_bwd_f64',
     'cbfssm_gp_adf_work_elems', 'cbfssm_gp_adf_f64', 'cbfssm_gp_ads_f64',
     'cbfssm_gp_adf_bwd_work_elems', 'cbfssm_gp_adf_bwd_f64',
 )
@@ -210,6 +211,9 @@ def load():
     lib.cbfssm_gp_moment_match_bwd_work_elems.restype = i64
     lib.cbfssm_gp_moment_match_bwd_work_elems.argtypes = [C.POINTER(PackLayout)]
     lib.cbfssm_gp_moment_match_bwd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cbfssm_gp_moment_match_params_bwd_work_elems.restype = i64
+    lib.cbfssm_gp_moment_match_params_bwd_work_elems.argtypes = [C.POINTER(PackLayout), i64]
+    lib.cbfssm_gp_moment_match_params_bwd_f64.argtypes = [C.POINTER(PackLayout), vp, vp, vp, vp, i64] + [vp] * 10
     lib.cbfssm_gp_ekf_work_elems.restype = i64
     lib.cbfssm_gp_ekf_work_elems.argtypes = [C.POINTER(PackLayout)]
     lib.cbfssm_gp_ekf_f64.argtypes = [C.POINTER(PackLayout)] + [vp] * 8 + [ip, i64, i64] + [vp] * 5

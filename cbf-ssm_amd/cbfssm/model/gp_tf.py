@@ -467,7 +467,7 @@ class GPModel:
         A = dmean[:, :, :Do] + torch.eye(Do, dtype=torch.float64, device=dev)
         return A, dmean[:, :, Do:].contiguous()
 
-    def moment_match(self, mean, cov, cross=True, input_grads=False):
+    def moment_match(self, mean, cov, cross=True, input_grads=False, differentiable=False):
         """An addition to the reference's surface: the exact moments of the GP output under a Gaussian input
         x[n] ~ N(mean[n], cov[n]) -- the moment matching of PILCO and of the GP assumed-density filter, closed form for the
         RBF kernel, where `linearize` is first order at the mean -- as one launch:
@@ -493,6 +493,18 @@ class GPModel:
         is a constant of the call -- the values its leaves had at the call: the five leaves get no gradient from these
         results whatever their requires_grad says (their .grad stays None, torch.autograd.grad(loss, leaf) fails as for any
         unconnected tensor).  Where info[n] != 0 the rows of point n of both gradients are NaN.
+
+        differentiable=True (the keyword of `ekf`; it takes precedence over input_grads): when grad is enabled and a leaf,
+        `mean` or `cov` requires it, the pack is prepared from the leaves and fmean, fcov and xcov (bitwise the values of
+        the evaluation call) carry a grad_fn into the five leaves of `parameters()` AND into mean and cov
+        (cbfssm.hip.autograd.gp_moment_match_params): the input adjoint launch, then the model adjoint -- a per-point pass
+        and a tile-outer pass that deliver one slab -- and the tail that `predict` and `ekf` use.  So a loss of a
+        moment-matched belief trains the inducing outputs, their variances, the inducing inputs, the lengthscales and the
+        signal variance.  The conventions are those above (lower triangle of cov, unused results, cov=None: the leaf
+        gradients are then those of `predict` for gmean = gfmean, gvar = diag gfcov); without a point nothing is prepared or
+        launched and the leaf gradients are zeros; where info[n] != 0 all five leaf gradients are NaN as well.  If nothing
+        requires grad, or grad is disabled, the call is the evaluation call.  Once differentiable, float64, no host
+        synchronisation.
         Raises ValueError on a q_full=True model."""
         self._no_full_q('moment_match')
         from ..hip import autograd as _ag
@@ -502,12 +514,14 @@ class GPModel:
         if cov is not None:
             cov = _f64(cov, dev)
             assert tuple(cov.shape) == (mean.shape[0], self.in_dim, self.in_dim), 'cov (N, in_dim, in_dim)'
+        if differentiable and self._wants_grad(mean, cov):
+            return _ag.gp_moment_match_params(self._pack, mean, cov, *self.parameters(), cross=cross)
         pack = self._prepared() if mean.shape[0] else self._pack                 # (nothing runs without a point)
         if input_grads:
             return _ag.gp_moment_match(pack, mean, cov, cross=cross)
         return _ag.gp_moment_match_eval(pack, mean, cov, cross=cross)
 
-    def transition_moments(self, h, P, a=None, input_grads=False):
+    def transition_moments(self, h, P, a=None, input_grads=False, differentiable=False):
         """The Gaussian one-step prediction of the recurrence `rollout`, `filter` and `ekf` run, h+ = h + f(concat(h, a)),
         for a belief h ~ N(h[n], P[n]) and a known input a (input covariance blockdiag(P, 0)), by `moment_match`:
 
@@ -519,6 +533,9 @@ class GPModel:
         is the caller's to add; info as in `moment_match`.  Evaluation only by default; input_grads=True: m+, P+ and cross
         carry a grad_fn into h, P (the gradient of the function of its lower triangle) and a when one of them requires it --
         `moment_match(..., input_grads=True)` with the tensor-library steps around it on the tape; the model is a constant.
+        differentiable=True: `moment_match(..., differentiable=True)` with the same steps on the tape -- m+, P+ and cross
+        carry a grad_fn into the five leaves as well, so a Python loop over this call with tensor-library Kalman updates is
+        a differentiable GP-ADF whose -loglik trains the model.
         Raises ValueError on a q_full=True model and when in_dim < out_dim."""
         self._no_full_q('transition_moments')
         Do, Da = self.out_dim, self.in_dim - self.out_dim
@@ -540,7 +557,7 @@ class GPModel:
             X = torch.cat([h, a], dim=1)
             S = torch.zeros(h.shape[0], self.in_dim, self.in_dim, dtype=torch.float64, device=dev)
             S[:, :Do, :Do] = Pl
-        fmean, fcov, xcov, info = self.moment_match(X, S, input_grads=input_grads)
+        fmean, fcov, xcov, info = self.moment_match(X, S, input_grads=input_grads, differentiable=differentiable)
         Cm = xcov[:, :, :Do].transpose(1, 2)                                     # Cov(h, f)
         low = torch.tril(P + Cm + Cm.transpose(1, 2) + fcov)
         Pn = low + torch.tril(low, -1).transpose(1, 2)

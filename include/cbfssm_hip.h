@@ -325,6 +325,40 @@ int cbfssm_gp_moment_match_bwd_f64(const cbfssm_pack_layout* layout, const doubl
                                    const double* gxcov, double* gmean, double* gcov, double* info, double* work, void* stream);
 
 /*
+ * The adjoint of cbfssm_gp_moment_match_f64 with respect to the MODEL: what the five leaves behind the pack receive through
+ * alpha = K^-1 mu, W_d, Z / lengthscale, the lengthscales and the variance, as ONE reduced slab in the slab layout of the
+ * parameter adjoints of one GP (sections gMu, gS2, gB, gZ; glx, gsig, glogsig; the var_x / var_y entries zero), which
+ * cbfssm_gp_tail_f64 (kl_weight 0) takes as it is.
+ *
+ * cbfssm_gp_moment_match_params_bwd_f64: pack, mean, cov, npts and the three cotangents as in
+ *   cbfssm_gp_moment_match_bwd_f64 (each NULL for a zero cotangent, all three NULL: -1); cflat: the constrained flat vector
+ *   the pack was prepared from (zeta_pos [M][D] | zeta_mean [M][Do] | zeta_var [M][Do] | variance [1] | lengthscales [D]);
+ *   gmean, gcov: the results of cbfssm_gp_moment_match_bwd_f64 for the same call (gcov NULL exactly when cov is) -- the
+ *   lengthscales reach the belief only through mean / l, cov / (l l^T) and the scaling of xcov, so the belief's side of their
+ *   adjoint is the contraction of the input adjoint with the inputs; xcov: the forward's result, read only with gxcov.
+ *   -> red_slab (layout->rev_slab doubles), every entry written, rows and columns >= M exactly zero; gB_dense: the K^-1
+ *   adjoint as a row-major [M][M] matrix (hand it to the tail with gB_ld = M), required exactly when layout->rev_stash
+ *   (the slab then has no such section), else NULL.  The Z~ section carries the adjoint of Z / lengthscale itself; its ones
+ *   column is zero.  A point with a non-positive pivot contributes exact zeros and makes every data entry of the slab and of
+ *   gB_dense NaN, by select.
+ *   Launches: alpha and (with gfcov) W_d from the dense K^-1; a per-point pass (factorisations, substitutions, the mean-side
+ *   terms; t_i = B^-1 r_i, g_i, m~, log c2 and the flag per point into `work`); with gfcov a tile-outer pass -- one
+ *   workgroup per 16 x 16 tile of the M x M images and chunk of points, the Do + 1 accumulators of an entry in registers --;
+ *   the fixed-order sums; X_d = K^-1 Wbar_d; the slab.  `work`: cbfssm_gp_moment_match_params_bwd_work_elems(layout, npts)
+ *   doubles, sized by the launch.
+ * No atomics, no allocation, no host synchronisation, one writer per entry, every sum in a fixed order: two calls are
+ * bitwise identical; nothing is launched at npts = 0.  Limits as cbfssm_gp_predict_f64 and a layout with an adjoint slab,
+ * else -3 before any launch; NULL layout, pack, cflat, mean, gmean, red_slab or work, no cotangent, gcov without cov or cov
+ * without gcov, gxcov without xcov, gB_dense against layout->rev_stash, or npts < 0: -1.  The count is host arithmetic in 64
+ * bits and returns -1 for a bad layout or npts < 0.
+ */
+int64_t cbfssm_gp_moment_match_params_bwd_work_elems(const cbfssm_pack_layout* layout, int64_t npts);  /* gp_tf.py:132-161 */
+int cbfssm_gp_moment_match_params_bwd_f64(const cbfssm_pack_layout* layout, const double* pack, const double* cflat,  /* gp_tf.py:132-161 */
+                                          const double* mean, const double* cov, int64_t npts, const double* gfmean,
+                                          const double* gfcov, const double* gxcov, const double* gmean, const double* gcov,
+                                          const double* xcov, double* red_slab, double* gB_dense, double* work, void* stream);
+
+/*
  * Assumed-density (moment-matching) Kalman filter over the transition of one sparse GP, and the Rauch-Tung-Striebel
  * smoother behind it: the recursion of cbfssm_gp_ekf_f64 with the exact moments of cbfssm_gp_moment_match_f64 in place of
  * the linearisation at the mean (GP-ADF).  Per chain n and step t, with x = concat(m, a[t]) and S = blockdiag(P, 0):
